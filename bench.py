@@ -1,8 +1,13 @@
 #!/usr/bin/env python
 """bench.py — FASTQ -> k-mer histogram throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run generates the batch, warms up, times K steps, writes the last step's result if --dump-outputs is given and
+prints the result line (metric, value, unit, ms_per_step, config): nothing else.  --full adds, after the timed steps,
+everything else this file measures or checks: the per-kernel timers and the roofline, the full-size parity of the
+result, the host-fed leg, the CPU baseline and the secondary workloads (`extra`).
 
 A step = one pass of the whole hot path (newline scan + validation, field table, ragged gather + 2-bit
 encode, 31-mer hashes generated straight into an MSD radix partition, in-LDS finishing sort + run-length
@@ -11,7 +16,7 @@ over one HBM-resident batch of synthetic FASTQ: ``--reads`` reads of ``--read-le
 scaling; default 50 M x 150 bp = BASELINE config 2, 15.8 GB of text, 7.5 Gbases, 6.0 G 31-mers per GPU).
 The input is generated on the device before the timed region; nothing is cached between steps.
 
-Rank 0 prints ONE JSON line: value = Gbases/s of the whole job (all GPUs), plus
+Rank 0 prints ONE JSON line: value = Gbases/s of the whole job (all GPUs), plus, under --full,
   roofline     — the dominant kernel of the step: algorithmic bytes per launch / its hipEvent-measured
                  average launch duration vs the 8 TB/s HBM peak (DESIGN.md §5 states the byte model)
   cpu_baseline — the numpy oracle (a statement-by-statement port of the reference's numpy path, which
@@ -620,6 +625,45 @@ def from_file_mode(args, ops, dev, mode, rank, world):
         sys.exit(4)
 
 
+DUMP_SAMPLE = 1 << 20          # --dump-outputs: elements written of each array of a larger result (5 arrays: 40 MiB)
+
+
+def dump_outputs(directory, hist, stats, seed, rank, world):
+    """--dump-outputs DIR: what fastq_kmer_histogram returned in the last timed step, as float64 .npy files.  A sparse
+    histogram is (keys, counts): keys.npy holds the int64 keys rounded to float64, keys_hi.npy / keys_lo.npy their bits above
+    and below bit 31, which float64 holds exactly.  A result of more than DUMP_SAMPLE elements is written at DUMP_SAMPLE
+    positions drawn with --seed (sorted, the first and the last element among them; positions.npy) — the same positions for
+    the same arguments; summary.npy = [elements of the whole result, sum of all counts, reads, bases, k-mers, bytes of text]"""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    sparse = isinstance(hist, tuple)
+    arrays = {"keys": hist[0], "counts": hist[1]} if sparse else {"histogram": hist}
+    n = (hist[0] if sparse else hist).size
+    pos = None
+    if n > DUMP_SAMPLE:
+        p = np.random.default_rng(seed).integers(0, n, size=DUMP_SAMPLE, dtype=np.int64)
+        p[0], p[1] = 0, n - 1
+        p.sort()
+        pos = torch.from_numpy(p).cuda()
+    prefix = "" if world == 1 else "rank%d_" % rank
+
+    def save(name, a):
+        np.save(os.path.join(directory, prefix + name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+    for name, a in arrays.items():
+        d = a.dev()
+        picked = (d if pos is None else d[pos]).cpu().numpy()
+        save(name, picked)
+        if name == "keys":
+            save("keys_hi", picked >> 31)
+            save("keys_lo", picked & ((1 << 31) - 1))
+    if pos is not None:
+        save("positions", pos.cpu().numpy())
+    total = int((hist[1] if sparse else hist).dev().sum().item()) if n else 0
+    save("summary", [n, total, stats.n_reads, stats.n_bases, stats.n_kmers, stats.n_bytes])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -631,8 +675,13 @@ def main():
     ap.add_argument("--mode", choices=["uniform", "genome"], default="uniform")
     ap.add_argument("--genome-len", type=int, default=100_000_000)
     ap.add_argument("--seed", type=int, default=20260925)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything else: per-kernel timers and roofline (the timers "
+                         "run during the timed steps), full-size parity of the result, host-fed leg, CPU baseline, secondary workloads")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the result of the last timed step as DIR/<name>.npy (float64; a seeded sample of a large result)")
     ap.add_argument("--cpu-sample-reads", type=int, default=400_000)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--virtual-ranks", type=int, default=0,
                     help="play the N-GPU sparse path on this one GPU: the batch is sharded N ways, the exchange is replaced "
                          "by its result, every rank's key range is counted (functional check of the N > 1 kernels, "
@@ -641,13 +690,13 @@ def main():
                     help="count the k-mers of this FASTQ file through the reader, every rank its part (written first — world x "
                          "--reads synthetic reads — if it does not exist); exits 4 if the ranks' reads do not add up")
     ap.add_argument("--file-chunk-mb", type=int, default=256, help="--from-file: chunk size the reader is asked for")
-    ap.add_argument("--no-host-fed", action="store_true", help="skip the host-fed (pinned RAM -> HBM) measurement")
+    ap.add_argument("--no-host-fed", action="store_true", help="--full: skip the host-fed (pinned RAM -> HBM) measurement")
     ap.add_argument("--host-fed-batches", type=int, default=2)
     ap.add_argument("--allow-fallback", action="store_true",
                     help="N > 1: accept torch.distributed's collectives if the C-ABI (RCCL) communicator cannot be made; without "
                          "this flag such a run FAILS instead of reporting a number measured on another path")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the secondary workloads (S-genome, config 3, config 5) that follow the timed region of `value`")
+                    help="--full: skip the secondary workloads (S-genome, config 3, config 5) that follow the timed region of `value`")
     ap.add_argument("--verify", action="store_true", help="check the first reads against the oracle")
     ap.add_argument("--canonical", action="store_true",
                     help="count strand-independent k-mers min(h, rc(h)) (extension; not the headline workload)")
@@ -703,8 +752,9 @@ def main():
         hist, stats = step()
         del hist
     barrier()
-    dev.prof_enable(True)
-    dev.prof_reset()
+    if args.full:                                            # the per-kernel hipEvent timers behind `kernels` and `roofline`
+        dev.prof_enable(True)
+        dev.prof_reset()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         hist, stats = step()
@@ -712,16 +762,24 @@ def main():
             del hist
     barrier()
     dt = time.perf_counter() - t0
-    dev.prof_enable(False)
-    prof = dev.prof_report()
+    prof = {}
+    if args.full:
+        dev.prof_enable(False)
+        prof = dev.prof_report()
 
-    # ---- parity of the FULL-SIZE result of the last step (outside the timed region; tests/fullsize.py) ------------
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, hist, stats, args.seed, rank, world)
+
+    # ---- --full: parity of the FULL-SIZE result of the last step (outside the timed region; tests/fullsize.py) ------------
     # sparse: order-independent checksums of the whole histogram against the k-mers in read order (another kernel),
     # plus the k-mers of reads sampled at the start / middle / end computed by the numpy oracle and looked up in the keys
-    sys.path.insert(0, os.path.join(ROOT, "tests"))
-    import fullsize
+    if args.full:
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import fullsize
     parity = None
-    if isinstance(hist, tuple):
+    if not args.full:
+        n_distinct = hist[0].size if isinstance(hist, tuple) else int((hist.dev() > 0).sum().item())
+    elif isinstance(hist, tuple):
         keys, counts = hist
         n_distinct = keys.size
         hs = fullsize.histogram_sums(keys, counts)
@@ -749,7 +807,8 @@ def main():
     per_rank = None
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
-        mine = torch.tensor([n_distinct, stats.n_kmers], dtype=torch.int64, device="cuda")
+    if world > 1 and args.full:
+        mine =torch.tensor([n_distinct, stats.n_kmers], dtype=torch.int64, device="cuda")
         gathered = [torch.empty_like(mine) for _ in range(world)]
         dist.all_gather(gathered, mine)
         per_rank = {"distinct_keys_held": [int(g[0]) for g in gathered], "kmers_generated": [int(g[1]) for g in gathered]}
@@ -784,6 +843,28 @@ def main():
     from bionumpy_amd import parallel
     merge = parallel.last
     gbases = world * stats.n_bases * args.steps / dt / 1e9
+    out = {
+        "metric": "Gbases/s FASTQ->k-mer count (k=%d)" % args.k,
+        "value": round(gbases, 4), "unit": "Gbases/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "int64", "data": "synthetic",
+        "config": {"workload": "synthetic %dbp x %d reads/GPU FASTQ (%s), k=%d get_kmers+count on %dxMI355X"
+                               % (args.read_len, args.reads, args.mode, args.k, world),
+                   "reads_per_gpu": args.reads, "read_len": args.read_len, "k": args.k, "mode": args.mode,
+                   "canonical": bool(args.canonical), "kmers_per_gpu": stats.n_kmers, "distinct_rank0": n_distinct,
+                   "histogram": "dense" if args.k <= 13 else "sparse (sorted unique int64 keys + counts)",
+                   "parallelism": "chunk-sharded x%d%s" % (world, ", key-range exchange of %s over %s" % (
+                       {"keys": "raw hashes in %s steps overlapped with the counting" % merge.get("groups"),
+                        "counts": "(key, count) runs of the local histograms"}.get(merge["plan"], "dense bins"),
+                       merge["collectives"]) if world > 1 else "")},
+    }
+    if not args.full:                                        # a plain run ends here: the headline and what it was measured on
+        print(json.dumps(out))
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: everything else this file measures or checks ---------------------------------------------------------
     # dominant kernel and its roofline
     dom = max(prof, key=lambda kname: prof[kname]["total_ms"]) if prof else None
     roofline = None
@@ -851,20 +932,7 @@ def main():
                     "guide_copy_gb_per_s": 6290.0,           # MI355X_MICROARCH.md: float4 copy, 79 % of the spec peak
                     "frac_of_measured_copy": None if (achieved is None or not measured_peak) else round(achieved / measured_peak, 4),
                     "algorithmic_bytes_per_launch": b}
-    out = {
-        "metric": "Gbases/s FASTQ->k-mer count (k=%d)" % args.k,
-        "value": round(gbases, 4), "unit": "Gbases/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 2), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "int64", "data": "synthetic",
-        "config": {"workload": "synthetic %dbp x %d reads/GPU FASTQ (%s), k=%d get_kmers+count on %dxMI355X"
-                               % (args.read_len, args.reads, args.mode, args.k, world),
-                   "reads_per_gpu": args.reads, "read_len": args.read_len, "k": args.k, "mode": args.mode,
-                   "canonical": bool(args.canonical), "kmers_per_gpu": stats.n_kmers, "distinct_rank0": n_distinct,
-                   "histogram": "dense" if args.k <= 13 else "sparse (sorted unique int64 keys + counts)",
-                   "parallelism": "chunk-sharded x%d%s" % (world, ", key-range exchange of %s over %s" % (
-                       {"keys": "raw hashes in %s steps overlapped with the counting" % merge.get("groups"),
-                        "counts": "(key, count) runs of the local histograms"}.get(merge["plan"], "dense bins"),
-                       merge["collectives"]) if world > 1 else "")},
+    out.update({
         "roofline": roofline,
         "kernels": kernels,
         "per_rank": per_rank,
@@ -873,7 +941,7 @@ def main():
         # what bnpk_count_sparse (ONE C-ABI call since round 6: csrc/sparse.hip) reported about the last step's histogram —
         # path 1 = claiming level + strided finish, 2 = plain levels, 3 = library sort; host round trips inside the call
         "planner": getattr(ops, "last_sparse_info", None),
-    }
+    })
     # ---- the same workload fed from page-locked host memory (never `value`): H2D on its own stream, overlapped ----------
     out["host_fed"] = None
     if world == 1 and not args.no_host_fed and args.k > 13 and isinstance(hist, tuple):

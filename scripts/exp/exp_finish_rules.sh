@@ -1,7 +1,7 @@
 # which finishing path the low-coverage shapes should take: the multiplicity kernel (5), the workgroup table (3) or the whole
 # cascade (4), against what mode 0 picks, on reads of a genome at several coverages   usage: exp_finish_rules.sh "4 5 8" "0 3 5"
 cd $GRAFT_REPO_ROOT
-B="python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-host-fed --no-extra"
+B="python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-host-fed --no-extra"
 show() { python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])

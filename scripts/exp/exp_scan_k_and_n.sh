@@ -1,6 +1,6 @@
 # the headline step at other k and other batch sizes: ms, Gbases/s, which finishing path, the planner's notes
 cd $GRAFT_REPO_ROOT
-B="python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-host-fed --no-extra"
+B="python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-host-fed --no-extra"
 show() { python -c "
 import json,sys
 try:

@@ -1,6 +1,6 @@
 # kernel breakdown of the shapes that lie off the headline's line (canonical k-mers, batches around 6.8e9 keys)
 cd $GRAFT_REPO_ROOT
-B="python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-host-fed --no-extra"
+B="python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-host-fed --no-extra"
 show() { python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])

@@ -2,8 +2,8 @@ set -x
 cd $GRAFT_REPO_ROOT
 R=gpurun_out/r06
 mkdir -p $R
-timeout 900 python bench.py --steps 5 --warmup 2 > $R/bench_50m_n1.json 2> $R/bench.err; cut -c1-400 $R/bench_50m_n1.json
-B="python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-host-fed --no-extra"
+timeout 900 python bench.py --full --steps 5 --warmup 2 > $R/bench_50m_n1.json 2> $R/bench.err; cut -c1-400 $R/bench_50m_n1.json
+B="python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-host-fed --no-extra"
 timeout 300 $B --k 21 > $R/bench_50m_n1_k21.json 2>> $R/bench.err
 timeout 300 $B --mode genome --genome-len 7500000000 > $R/bench_50m_n1_genome_1x.json 2>> $R/bench.err
 timeout 300 $B --mode genome --genome-len 2500000000 > $R/bench_50m_n1_genome_3x.json 2>> $R/bench.err

@@ -9,7 +9,7 @@ OUT=$REPO/gpurun_out/prof$1
 shift
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-COMMON="--no-cpu-baseline --no-host-fed --no-extra $*"
+COMMON="--full --no-cpu-baseline --no-host-fed --no-extra $*"
 rocprofv3 --kernel-trace --stats -d $OUT/stats -o bench -- python $REPO/bench.py $COMMON --steps 2 --warmup 1 > $OUT/bench_stats.json 2> $OUT/bench_stats.err
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_fetch -o bench -- python $REPO/bench.py $COMMON --steps 1 --warmup 0 > $OUT/bench_fetch.json 2> $OUT/bench_fetch.err
 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/pmc_write -o bench -- python $REPO/bench.py $COMMON --steps 1 --warmup 0 > $OUT/bench_write.json 2> $OUT/bench_write.err

@@ -1,6 +1,6 @@
 # other shapes of the headline step through the C planner (round 6): every line must say parity_fullsize true
 cd $GRAFT_REPO_ROOT
-B="python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-host-fed --no-extra"
+B="python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-host-fed --no-extra"
 show() { python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])

@@ -36,7 +36,7 @@ if copies and max(c[3] for c in copies) == 0:              # no byte counts in t
     copies = [(s, e, d, chunk_bytes if (e - s) > 5_000_000 and "HOST_TO_DEVICE" in d.upper().replace(" ", "_") else 0)
               for s, e, d, _ in copies]
 big = [c for c in copies if c[3] >= (1 << 28)]
-lines = ["# rocprofv3 --kernel-trace --memory-copy-trace -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline",
+lines = ["# rocprofv3 --kernel-trace --memory-copy-trace -- python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline",
          "# memory copies of at least 256 MiB (the host-fed leg's chunks; sizes taken as bench.py's chunk size where the trace "
          "has no size column, the last chunk of a batch is shorter): %d rows" % len(big),
          "# bench.py host_fed of the traced run: %s" % (json.dumps(hf) if hf else "?"),

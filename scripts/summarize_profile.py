@@ -101,7 +101,7 @@ def main():
     if os.path.exists(stats_db):
         text = kernel_stats(stats_db)
         bench = os.path.join(src, "bench_stats.json")
-        header = "# rocprofv3 --kernel-trace --stats -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-host-fed --no-extra [args of the profiled line below]\n"
+        header = "# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-host-fed --no-extra [args of the profiled line below]\n"
         if os.path.exists(bench):
             header += "# bench line of the profiled run: " + open(bench).read().strip()[:1500] + "\n"
         open(out + "_kernel_stats.txt", "w").write(header + text)
