@@ -122,6 +122,9 @@ SIGNATURES = {
     "bnpk_reverse_complement_packed": (_int, [_p, _p, _p, _i64, _i64, _p, _p]),
     "bnpk_reverse_complement_bytes": (_int, [_p, _p, _p, _i64, _i64, _p, _p]),
     "bnpk_reverse_complement_rows": (_int, [_p, _p, _i64, _p, _p, _i64, _i64, _p, _p]),
+    "bnpk_translate_plan": (_int, [_p, _p, _i64, _int, _p, _p, _p]),
+    "bnpk_translate_packed": (_int, [_p, _p, _p, _i64, _i64, _p, _i64, _p, _int, _int, _p, _p]),
+    "bnpk_translate_rows": (_int, [_p, _p, _i64, _p, _p, _i64, _i64, _p, _i64, _p, _int, _int, _u8, _p, _p, _p]),
     "bnpk_canonical_kmers": (_int, [_p, _p, _i64, _int, _p]),
     "bnpk_windows_flat": (_int, [_p, _p, _p, _i64, _int, _int, _i64, _p, _p]),
     "bnpk_match_windows_packed": (_int, [_p, _p, _p, _i64, _int, C.c_uint64, _i64, _p, _p]),

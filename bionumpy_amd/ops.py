@@ -578,6 +578,50 @@ class HipOps:
                                                    total, ptr(out), self._s()))
         return HArray(dev=out)
 
+    # -- DNA -> protein (sequence/translate.py) ------------------------------------------------------------------
+    def translate_plan(self, in_offsets, n_rows, frame):
+        """(letters per row, their offsets[n+1], number of letters, number of rows with (length - frame) % 3 != 0)"""
+        out_lens = self._empty(n_rows, np.int64)
+        if n_rows == 0:
+            return HArray(dev=out_lens), self.exclusive_scan(HArray(dev=out_lens)), 0, 0
+        cell = self._empty(1, np.int64)
+        self._chk(lib.bnpk_translate_plan(self.ctx, ptr(in_offsets.dev()), n_rows, frame, ptr(out_lens), ptr(cell), self._s()))
+        out_offsets = self.exclusive_scan(HArray(dev=out_lens))
+        n_out = self._fetch(out_offsets.dev()[n_rows:], 1)[0]
+        return HArray(dev=out_lens), out_offsets, n_out, self._fetch(cell, 1)[0]
+
+    @staticmethod
+    def _table64(table):
+        table = np.ascontiguousarray(table, dtype=np.uint8)
+        assert table.size == 64, "a codon table has 64 letters"
+        return table
+
+    def translate_packed(self, packed, in_offsets, n_rows, total, out_offsets, n_out, table, frame, reverse):
+        """the amino-acid letters of 2-bit DNA rows (bnpk_translate_packed), compact ASCII"""
+        out = self._empty(n_out, np.uint8)
+        table = self._table64(table)
+        self._chk(lib.bnpk_translate_packed(self.ctx, ptr(packed.dev()), ptr(in_offsets.dev()), n_rows, total,
+                                            ptr(out_offsets.dev()), n_out, table.ctypes.data_as(C.c_void_p), frame,
+                                            1 if reverse else 0, ptr(out), self._s()))
+        return HArray(dev=out)
+
+    def translate_rows(self, buf, starts, in_offsets, n_rows, total, out_offsets, n_out, table, frame, reverse, unknown=0):
+        """the amino-acid letters of ASCII rows where they lie (bnpk_translate_rows; starts None: buf is compact).  unknown
+        0: EncodingError(flat offset of the first byte inside a translated codon that is not A C G T); else that letter"""
+        out = self._empty(n_out, np.uint8)
+        table = self._table64(table)
+        cell = self._err_cell()
+        self._chk(lib.bnpk_translate_rows(self.ctx, ptr(buf.dev()), buf.size, ptr(starts.dev()) if starts is not None else None,
+                                          ptr(in_offsets.dev()), n_rows, total, ptr(out_offsets.dev()), n_out,
+                                          table.ctypes.data_as(C.c_void_p), frame, 1 if reverse else 0, unknown, ptr(cell),
+                                          ptr(out), self._s()))
+        if not unknown:
+            off = self._fetch(cell, 1)[0]
+            if off != NONE:
+                raise EncodingError("Error when encoding to AlphabetEncoding('TCAG'): invalid character at flat "
+                                    "offset %d" % off, off)
+        return HArray(dev=out)
+
     def canonical_kmers(self, hashes, k):
         """h = min(h, hash of the reverse complement k-mer); overwrites the device buffer of ``hashes``"""
         t = hashes.dev()

@@ -2,6 +2,8 @@
 from .kmers import get_kmers, count_kmers, KmerEncoder
 from .minimizers import get_minimizers, Minimizers
 from .dna import get_reverse_complement
+from . import translate
+from .translate import translate_dna_to_protein
 from .string_matcher import match_string
 from . import string_matcher
 from . import position_weight_matrix
@@ -12,5 +14,5 @@ from .indexing import KmerIndex, KmerLookup
 from . import debruin
 from .debruin import DeBruijnGraph, ColoredDeBruijnGraph
 
-__all__ = ["get_kmers", "count_kmers", "KmerEncoder", "Minimizers", "PositionWeightMatrix", "get_minimizers", "get_reverse_complement", "match_string", "string_matcher", "PWM", "get_motif_scores", "position_weight_matrix", "count_encoded", "EncodedCounts", "SparseKmerCounts",
+__all__ = ["get_kmers", "count_kmers", "KmerEncoder", "Minimizers", "PositionWeightMatrix", "get_minimizers", "get_reverse_complement", "translate_dna_to_protein", "translate", "match_string", "string_matcher", "PWM", "get_motif_scores", "position_weight_matrix", "count_encoded", "EncodedCounts", "SparseKmerCounts",
            "KmerIndex", "KmerLookup", "indexing", "debruin", "DeBruijnGraph", "ColoredDeBruijnGraph"]

@@ -431,6 +431,32 @@ int bnpk_reverse_complement_bytes(bnpk_ctx* ctx, const uint8_t* d_bytes, const i
 int bnpk_reverse_complement_rows(bnpk_ctx* ctx, const uint8_t* d_bytes, int64_t in_size, const int64_t* d_in_starts,
                                  const int64_t* d_offsets, int64_t n_rows, int64_t total, uint8_t* d_out, void* stream);
 
+/* ---- DNA -> protein translation ------------------------------------------------------------------------
+ * replaces translate_dna_to_protein / Translate().windowed (bionumpy/sequence/translate.py): row r of L_r bases gives
+ * P_r = max(0, L_r - frame) / 3 ASCII amino-acid letters, frame in {0, 1, 2}.  reverse = 0: codon j is bases
+ * frame + 3j .. frame + 3j + 2; reverse = 1: codon j of the row's reverse complement (bases L - 1 - frame - 3j down to
+ * L - 3 - frame - 3j, complemented).  The frame's leading bases and the 1-2 bases no codon covers are ignored.
+ * table64: HOST pointer to the 64 letters in the reference's order, index 16 c0 + 4 c1 + c2 with T C A G = 0 1 2 3 and
+ * c0 the codon's first base (translate.py:13-14).  The output is compact: d_out_offsets (n_rows+1) = exclusive scan of
+ * P_r, n_out = its last entry.  n_rows == 0 or n_out == 0: BNPK_OK, nothing launched.
+ *   _plan:   d_out_lens[r] = P_r (scan it with bnpk_exclusive_scan_i64), *d_partial_rows = number of rows with
+ *            (L_r - frame) % 3 != 0 (the reference refuses those).
+ *   _packed: 2-bit DNA in the bnpk_gather_encode_dna layout (total/32 + 2 words).
+ *   _rows:   ASCII, either letter case; row r is d_bytes[d_in_starts[r] ..) of a buffer of in_size bytes, or, with
+ *            d_in_starts NULL, d_bytes[d_in_offsets[r] ..).  Only the bytes INSIDE translated codons are examined:
+ *            unknown == 0: *d_err_cell (preset to BNPK_NONE) = min(itself, flat offset — position in the concatenated
+ *            rows, as bnpk_gather_encode_dna reports it — of every such byte that is not A C G T); unknown != 0: a
+ *            codon holding such a byte gives the letter `unknown` and nothing is reported. */
+int bnpk_translate_plan(bnpk_ctx* ctx, const int64_t* d_in_offsets, int64_t n_rows, int frame, int64_t* d_out_lens,
+                        int64_t* d_partial_rows, void* stream);
+int bnpk_translate_packed(bnpk_ctx* ctx, const uint64_t* d_packed, const int64_t* d_in_offsets, int64_t n_rows, int64_t total,
+                          const int64_t* d_out_offsets, int64_t n_out, const uint8_t* table64, int frame, int reverse,
+                          uint8_t* d_out, void* stream);
+int bnpk_translate_rows(bnpk_ctx* ctx, const uint8_t* d_bytes, int64_t in_size, const int64_t* d_in_starts,
+                        const int64_t* d_in_offsets, int64_t n_rows, int64_t total, const int64_t* d_out_offsets, int64_t n_out,
+                        const uint8_t* table64, int frame, int reverse, uint8_t unknown, int64_t* d_err_cell, uint8_t* d_out,
+                        void* stream);
+
 /* In place h[i] = min(h[i], rc(h[i])), rc(h) = the hash (layout of bnpk_kmers, first base least significant) of the
  * reverse complement of the k-mer with hash h: strand-independent ("canonical") k-mers.  Not in the reference;
  * defined by the oracle (oracle/kmers.py: canonical_kmers) on top of get_reverse_complement. */
