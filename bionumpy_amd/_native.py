@@ -130,6 +130,9 @@ SIGNATURES = {
     "bnpk_match_windows_packed": (_int, [_p, _p, _p, _i64, _int, C.c_uint64, _i64, _p, _p]),
     "bnpk_match_windows_bytes": (_int, [_p, _p, _p, _i64, _int, _p, _i64, _p, _p]),
     "bnpk_match_rows_packed": (_int, [_p, _p, _i64, _p, _i64, _int, C.c_uint64, _p, _p]),
+    "bnpk_motif_flags_packed": (_int, [_p, _p, _p, _i64, _p, _p, _p]),
+    "bnpk_motif_flags_bytes": (_int, [_p, _p, _p, _i64, _p, _p, _p]),
+    "bnpk_motif_rows_packed": (_int, [_p, _p, _i64, _p, _i64, _p, _p, _p]),
     "bnpk_pwm_scores": (_int, [_p, _p, _p, _i64, _int, _p, _i64, _p, _p]),
     "bnpk_kmers_partition": (_int, [_p, _p, _p, _i64, _int, _int, _int, _int, _p, _p, _p]),
     "bnpk_minimizers": (_int, [_p, _p, _p, _p, _i64, _i64, _int, _int, _p, _p]),
@@ -167,6 +170,16 @@ SIGNATURES = {
     "bnpk_synth_record_bytes": (_i64, [_int]),
     "bnpk_synth_fastq": (_int, [_p, _p, _i64, _i64, _int, C.c_uint64, _int, _i64, _p]),
 }
+
+MOTIF_MAX_SPAN, MOTIF_MAX_CLASSES, MOTIF_ANY = 64, 16, 255
+
+
+class Motif(C.Structure):
+    """bnpk_motif of include/bnpk.h: a compiled class-and-gap pattern"""
+    _fields_ = [("n_segments", C.c_int32), ("n_classes", C.c_int32),
+                ("seg_len", _u8 * MOTIF_MAX_SPAN), ("gap_min", _u8 * MOTIF_MAX_SPAN), ("gap_max", _u8 * MOTIF_MAX_SPAN),
+                ("pos_class", _u8 * MOTIF_MAX_SPAN), ("class_set4", _u8 * MOTIF_MAX_CLASSES), ("class_mask", C.c_uint16 * 256)]
+
 
 for _name, (_res, _args) in SIGNATURES.items():
     _f = getattr(lib, _name)          # AttributeError here == symbol missing from the build

@@ -431,6 +431,37 @@ class HipOps:
                                                  len(pattern), h, ptr(out), self._s()))
         return HArray(dev=out)
 
+    # -- class-and-gap motifs (sequence/string_matcher.py: the matcher classes) ------------------------------------------------
+    def row_end_mask(self, offsets, n_rows, total):
+        """one bit per symbol, set on the last symbol of every non-empty row (bnpk_row_end_mask)"""
+        ends = self._empty(total // 64 + 2, np.int64)
+        self._chk(lib.bnpk_row_end_mask(self.ctx, ptr(offsets.dev()), n_rows, total, ptr(ends), self._s()))
+        return HArray(dev=ends)
+
+    def motif_flags(self, data, offsets, n_rows, total, program, packed, row_ends=None):
+        """uint8 0/1 per symbol of the flat column: a match of the compiled motif (a ``_native.Motif``) starts there and lies
+        inside its row.  packed: ``data`` = 2-bit words (bnpk_motif_flags_packed), else one code byte per symbol
+        (bnpk_motif_flags_bytes)"""
+        out = self._empty(total, np.uint8)
+        if total == 0:
+            return HArray(dev=out)
+        ends = row_ends if row_ends is not None else self.row_end_mask(offsets, n_rows, total)
+        call = lib.bnpk_motif_flags_packed if packed else lib.bnpk_motif_flags_bytes
+        src = data.dev()
+        if src.data_ptr() % 16:                              # (a slice of somebody's buffer: the byte kernel loads 16 bytes at a time)
+            src = src.clone()
+        self._chk(call(self.ctx, ptr(src), ptr(ends.dev()), total, C.byref(program), ptr(out), self._s()))
+        return HArray(dev=out)
+
+    def motif_rows(self, packed, offsets, n_rows, total, program):
+        """int64 per row: the starts in it at which the motif matches, from the 2-bit words — the flags of motif_flags summed
+        per row without being written (bnpk_motif_rows_packed)"""
+        out = self._empty(n_rows, np.int64)
+        if n_rows:
+            self._chk(lib.bnpk_motif_rows_packed(self.ctx, ptr(packed.dev()) if total else None, total, ptr(offsets.dev()), n_rows,
+                                                 C.byref(program), ptr(out), self._s()))
+        return HArray(dev=out)
+
     def pwm_scores(self, packed, offsets, n_rows, total, n_out, matrix):
         """float64 motif score of every window of matrix.shape[1] bases, ragged-flat; matrix[code][position]"""
         width = matrix.shape[1]

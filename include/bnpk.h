@@ -493,6 +493,42 @@ int bnpk_match_windows_bytes(bnpk_ctx* ctx, const uint8_t* d_bytes, const uint64
 int bnpk_match_rows_packed(bnpk_ctx* ctx, const uint64_t* d_packed, int64_t n_bases, const int64_t* d_offsets, int64_t n_rows,
                            int m, uint64_t pattern_hash, int64_t* d_counts, void* stream);
 
+/* ---- class-and-gap motifs (StringMatcher / MaskedStringMatcher / FixedLenRegexMatcher / RegexMatcher of
+ * bionumpy/sequence/string_matcher.py:45-177) ---------------------------------------------------------------------------
+ * The pattern comes compiled, not as text: a run of SEGMENTS, each a run of fixed positions that hold a class id or
+ * BNPK_MOTIF_ANY, with between segments k and k + 1 a gap of gap_min[k] .. gap_max[k] arbitrary symbols; a class is a set of
+ * symbol codes.  "[AG].[AT]" is one segment {0, ANY, 1} with the classes {A,G} and {A,T}; "AA.{,1}[CT]" is the segments
+ * {0, 0} and {1} with the gap 0 .. 1 and the classes {A} and {C,T}.  Limits: the longest possible match (all positions +
+ * all gap_max) is at most BNPK_MOTIF_MAX_SPAN symbols (BNPK_ERR_RANGE beyond), at most BNPK_MOTIF_MAX_CLASSES classes; a
+ * malformed program (no segment, an empty segment, gap_min > gap_max, a class id that does not exist) is BNPK_ERR_ARG.
+ *
+ * A match must lie inside one row.  The flags have the shape of the input ("same"): d_flags[i] = 1 iff a match STARTS at
+ * symbol i of the flat column (n symbols, 0 / 1 bytes, 16-byte aligned buffer), else 0; the last span - 1 flags of a row are
+ * therefore 0.  d_row_ends = bnpk_row_end_mask of the rows' offsets (n / 64 + 2 words).  n == 0: BNPK_OK, nothing launched.
+ *   _flags_packed: 2-bit symbols in the bnpk_gather_encode_dna layout (n / 32 + 2 words); the classes are class_set4.
+ *   _flags_bytes:  one byte per symbol (16-byte aligned buffer); the classes are class_mask.
+ *   _rows_packed:  d_counts[r] = the matching starts of row r (symbols d_offsets[r] .. d_offsets[r + 1]), without writing
+ *                  flags: what `.sum(axis=-1)` / `.any(axis=-1)` of the flags come to.  n_rows == 0: BNPK_OK. */
+#define BNPK_MOTIF_MAX_SPAN 64
+#define BNPK_MOTIF_MAX_CLASSES 16
+#define BNPK_MOTIF_ANY 255
+typedef struct {
+  int32_t n_segments;                               /* 1 .. BNPK_MOTIF_MAX_SPAN */
+  int32_t n_classes;                                /* 0 .. BNPK_MOTIF_MAX_CLASSES */
+  uint8_t seg_len[BNPK_MOTIF_MAX_SPAN];             /* fixed positions of segment k, >= 1 */
+  uint8_t gap_min[BNPK_MOTIF_MAX_SPAN];             /* symbols between segment k and k + 1 (k < n_segments - 1) */
+  uint8_t gap_max[BNPK_MOTIF_MAX_SPAN];
+  uint8_t pos_class[BNPK_MOTIF_MAX_SPAN];           /* the segments' positions one after the other: class id or BNPK_MOTIF_ANY */
+  uint8_t class_set4[BNPK_MOTIF_MAX_CLASSES];       /* 2-bit input: bit c = code c is in the class */
+  uint16_t class_mask[256];                         /* byte input: bit k of entry v = byte value v is in class k */
+} bnpk_motif;
+int bnpk_motif_flags_packed(bnpk_ctx* ctx, const uint64_t* d_packed, const uint64_t* d_row_ends, int64_t n_bases,
+                            const bnpk_motif* h_motif, uint8_t* d_flags, void* stream);
+int bnpk_motif_flags_bytes(bnpk_ctx* ctx, const uint8_t* d_bytes, const uint64_t* d_row_ends, int64_t n_bytes,
+                           const bnpk_motif* h_motif, uint8_t* d_flags, void* stream);
+int bnpk_motif_rows_packed(bnpk_ctx* ctx, const uint64_t* d_packed, int64_t n_bases, const int64_t* d_offsets, int64_t n_rows,
+                           const bnpk_motif* h_motif, int64_t* d_counts, void* stream);
+
 /* Position weight matrix scores (bionumpy/sequence/position_weight_matrix.py:86-104,177-196): for every
  * window of `width` <= 64 bases, in the ragged-flat order of the windows, the double-precision sum
  * ((0 + M[0][c_0]) + M[1][c_1]) + ... — the accumulation order of the reference's calculate_scores, so finite scores
