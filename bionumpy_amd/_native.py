@@ -133,6 +133,10 @@ SIGNATURES = {
     "bnpk_motif_flags_packed": (_int, [_p, _p, _p, _i64, _p, _p, _p]),
     "bnpk_motif_flags_bytes": (_int, [_p, _p, _p, _i64, _p, _p, _p]),
     "bnpk_motif_rows_packed": (_int, [_p, _p, _i64, _p, _i64, _p, _p, _p]),
+    "bnpk_bloom_insert_hashes": (_int, [_p, _p, _p, _i64, _p]),
+    "bnpk_bloom_query_hashes": (_int, [_p, _p, _p, _i64, _p, _p]),
+    "bnpk_bloom_insert_packed": (_int, [_p, _p, _p, _p, _i64, _p]),
+    "bnpk_bloom_rows_packed": (_int, [_p, _p, _p, _i64, _p, _i64, _p, _p]),
     "bnpk_pwm_scores": (_int, [_p, _p, _p, _i64, _int, _p, _i64, _p, _p]),
     "bnpk_kmers_partition": (_int, [_p, _p, _p, _i64, _int, _int, _int, _int, _p, _p, _p]),
     "bnpk_minimizers": (_int, [_p, _p, _p, _p, _i64, _i64, _int, _int, _p, _p]),
@@ -179,6 +183,12 @@ class Motif(C.Structure):
     _fields_ = [("n_segments", C.c_int32), ("n_classes", C.c_int32),
                 ("seg_len", _u8 * MOTIF_MAX_SPAN), ("gap_min", _u8 * MOTIF_MAX_SPAN), ("gap_max", _u8 * MOTIF_MAX_SPAN),
                 ("pos_class", _u8 * MOTIF_MAX_SPAN), ("class_set4", _u8 * MOTIF_MAX_CLASSES), ("class_mask", C.c_uint16 * 256)]
+
+
+class Bloom(C.Structure):
+    """bnpk_bloom of include/bnpk.h: a blocked Bloom filter over k-mers, its words in HBM"""
+    _fields_ = [("d_words", C.c_void_p), ("n_blocks", C.c_uint64), ("seed", C.c_uint64), ("n_hashes", C.c_int32),
+                ("k", C.c_int32), ("canonical", C.c_int32), ("reserved", C.c_int32)]
 
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -462,6 +462,38 @@ class HipOps:
                                                  C.byref(program), ptr(out), self._s()))
         return HArray(dev=out)
 
+    # -- blocked Bloom filter over k-mers (sequence/bloom_filter.py) ------------------------------------------------------------
+    # ``bloom``: a ``_native.Bloom`` whose d_words points at the filter's words in HBM
+    def bloom_insert_hashes(self, bloom, kmers):
+        """ORs int64 k-mer hashes into the filter (bnpk_bloom_insert_hashes)"""
+        if kmers.size:
+            self._chk(lib.bnpk_bloom_insert_hashes(self.ctx, C.byref(bloom), ptr(kmers.dev()), kmers.size, self._s()))
+
+    def bloom_query_hashes(self, bloom, kmers):
+        """uint8 0/1 per int64 k-mer hash: is it in the filter (bnpk_bloom_query_hashes)"""
+        out = self._empty(kmers.size, np.uint8)
+        if kmers.size:
+            src = kmers.dev()
+            if src.data_ptr() % 16:                              # (a slice of somebody's buffer: the kernel loads 16 bytes at a time)
+                src = src.clone()
+            self._chk(lib.bnpk_bloom_query_hashes(self.ctx, C.byref(bloom), ptr(src), kmers.size, ptr(out), self._s()))
+        return HArray(dev=out)
+
+    def bloom_insert_packed(self, bloom, packed, start_mask, n_bases):
+        """ORs the k-mers at the marked positions of 2-bit words into the filter, no hashes written (bnpk_bloom_insert_packed)"""
+        if n_bases:
+            self._chk(lib.bnpk_bloom_insert_packed(self.ctx, C.byref(bloom), ptr(packed.dev()), ptr(start_mask.dev()), n_bases,
+                                                   self._s()))
+
+    def bloom_rows(self, bloom, packed, offsets, n_rows, total):
+        """int64 per row: its k-mers that are in the filter, from the 2-bit words; neither hashes nor flags are written
+        (bnpk_bloom_rows_packed)"""
+        out = self._empty(n_rows, np.int64)
+        if n_rows:
+            self._chk(lib.bnpk_bloom_rows_packed(self.ctx, C.byref(bloom), ptr(packed.dev()) if total else None, total,
+                                                 ptr(offsets.dev()), n_rows, ptr(out), self._s()))
+        return HArray(dev=out)
+
     def pwm_scores(self, packed, offsets, n_rows, total, n_out, matrix):
         """float64 motif score of every window of matrix.shape[1] bases, ragged-flat; matrix[code][position]"""
         width = matrix.shape[1]

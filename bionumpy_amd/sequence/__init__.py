@@ -13,6 +13,9 @@ from . import indexing
 from .indexing import KmerIndex, KmerLookup
 from . import debruin
 from .debruin import DeBruijnGraph, ColoredDeBruijnGraph
+from . import bloom_filter
+from .bloom_filter import BloomFilter
 
 __all__ = ["get_kmers", "count_kmers", "KmerEncoder", "Minimizers", "PositionWeightMatrix", "get_minimizers", "get_reverse_complement", "translate_dna_to_protein", "translate", "match_string", "string_matcher", "PWM", "get_motif_scores", "position_weight_matrix", "count_encoded", "EncodedCounts", "SparseKmerCounts",
-           "KmerIndex", "KmerLookup", "indexing", "debruin", "DeBruijnGraph", "ColoredDeBruijnGraph"]
+           "KmerIndex", "KmerLookup", "indexing", "debruin", "DeBruijnGraph", "ColoredDeBruijnGraph",
+           "bloom_filter", "BloomFilter"]

@@ -529,6 +529,44 @@ int bnpk_motif_flags_bytes(bnpk_ctx* ctx, const uint8_t* d_bytes, const uint64_t
 int bnpk_motif_rows_packed(bnpk_ctx* ctx, const uint64_t* d_packed, int64_t n_bases, const int64_t* d_offsets, int64_t n_rows,
                            const bnpk_motif* h_motif, int64_t* d_counts, void* stream);
 
+/* ---- blocked Bloom filter over k-mers ("8 bits per kmer / cache optimized bloom filter", bionumpy/sequence/bloom_filter.py:
+ * the reference ships the class as a stub, its tests skipped) ------------------------------------------------------------
+ * The filter is n_blocks (1 <= n_blocks < 2^32, any number) 64-bit words in HBM that the caller owns and has zeroed.  A k-mer
+ * lives in one word:
+ *   h     = its hash in the layout of bnpk_kmers, k <= 31;  canonical != 0: h = min(h, rc(h)) as in bnpk_canonical_kmers
+ *   g     = fmix64(h ^ seed)        x ^= x >> 33; x *= 0xff51afd7ed558ccd; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33
+ *   block = ((g >> 32) * n_blocks) >> 32
+ *   bits  = OR over j < n_hashes (1 .. 5) of 1 << ((g >> 6 j) & 63)
+ *   insert: d_words[block] |= bits        query: (d_words[block] & bits) == bits
+ * Insertion is cumulative (call after call builds one filter) and atomic; there are no false negatives.  h_filter is a HOST
+ * pointer.  BNPK_ERR_ARG for k outside 1 .. 31 or n_hashes outside 1 .. 5, BNPK_ERR_RANGE for n_blocks outside its range;
+ * nothing to do (n == 0, n_bases == 0, n_rows == 0) is BNPK_OK.
+ *   _insert_hashes  replaces BloomFilter.insert (bloom_filter.py:37-39) for n int64 k-mers
+ *   _query_hashes   replaces BloomFilter.__getitem__ (bloom_filter.py:41-42): d_flags[i] = 1 if k-mer i is in the filter,
+ *                   else 0.  d_kmers 16-byte, d_flags 8-byte aligned (BNPK_ERR_ALIGN).
+ *   _insert_packed  BloomFilter.insert of get_kmers(sequences, k) without the hashes: the k-mers that start at the positions
+ *                   marked in d_start_mask (bnpk_kmer_start_mask / bnpk_kmer_starts_from_ends with this k) of 2-bit bases in
+ *                   the bnpk_gather_encode_dna layout.
+ *   _rows_packed    d_counts[r] = how many of the k-mers of row r (bases d_offsets[r] .. d_offsets[r + 1], d_offsets[n_rows]
+ *                   == n_bases) are in the filter: BloomFilter.__getitem__ of get_kmers(sequences, k), summed per row, with
+ *                   neither hashes nor flags written.  Rows shorter than k count 0. */
+typedef struct {
+  uint64_t* d_words;
+  uint64_t n_blocks;
+  uint64_t seed;
+  int32_t n_hashes;
+  int32_t k;
+  int32_t canonical;
+  int32_t reserved;
+} bnpk_bloom;
+int bnpk_bloom_insert_hashes(bnpk_ctx* ctx, const bnpk_bloom* h_filter, const int64_t* d_kmers, int64_t n, void* stream);
+int bnpk_bloom_query_hashes(bnpk_ctx* ctx, const bnpk_bloom* h_filter, const int64_t* d_kmers, int64_t n, uint8_t* d_flags,
+                            void* stream);
+int bnpk_bloom_insert_packed(bnpk_ctx* ctx, const bnpk_bloom* h_filter, const uint64_t* d_packed, const uint64_t* d_start_mask,
+                             int64_t n_bases, void* stream);
+int bnpk_bloom_rows_packed(bnpk_ctx* ctx, const bnpk_bloom* h_filter, const uint64_t* d_packed, int64_t n_bases,
+                           const int64_t* d_offsets, int64_t n_rows, int64_t* d_counts, void* stream);
+
 /* Position weight matrix scores (bionumpy/sequence/position_weight_matrix.py:86-104,177-196): for every
  * window of `width` <= 64 bases, in the ragged-flat order of the windows, the double-precision sum
  * ((0 + M[0][c_0]) + M[1][c_1]) + ... — the accumulation order of the reference's calculate_scores, so finite scores
