@@ -138,6 +138,8 @@ SIGNATURES = {
     "bnpk_bloom_insert_packed": (_int, [_p, _p, _p, _p, _i64, _p]),
     "bnpk_bloom_rows_packed": (_int, [_p, _p, _p, _i64, _p, _i64, _p, _p]),
     "bnpk_pwm_scores": (_int, [_p, _p, _p, _i64, _int, _p, _i64, _p, _p]),
+    "bnpk_pwm_rows_packed": (_int, [_p, _p, _p, _i64, _p, _i64, _int, _p, _p, _p, _p, _p]),
+    "bnpk_pwm_rows_bytes": (_int, [_p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p]),
     "bnpk_kmers_partition": (_int, [_p, _p, _p, _i64, _int, _int, _int, _int, _p, _p, _p]),
     "bnpk_minimizers": (_int, [_p, _p, _p, _p, _i64, _i64, _int, _int, _p, _p]),
     "bnpk_count_bytes": (_int, [_p, _p, _i64, _int, _p, _p]),
@@ -189,6 +191,15 @@ class Bloom(C.Structure):
     """bnpk_bloom of include/bnpk.h: a blocked Bloom filter over k-mers, its words in HBM"""
     _fields_ = [("d_words", C.c_void_p), ("n_blocks", C.c_uint64), ("seed", C.c_uint64), ("n_hashes", C.c_int32),
                 ("k", C.c_int32), ("canonical", C.c_int32), ("reserved", C.c_int32)]
+
+
+PWM_MAX_WIDTH, PWM_MAX_ALPHABET, PWM_MAX_MOTIFS, PWM_GROUP_MOTIFS = 64, 32, 4096, 16
+
+
+class PwmLibrary(C.Structure):
+    """bnpk_pwm_library of include/bnpk.h: widths, matrices ([position][code], one after the other) and thresholds on the host"""
+    _fields_ = [("n_motifs", C.c_int32), ("alphabet_size", C.c_int32), ("width", C.c_void_p), ("matrix", C.c_void_p),
+                ("threshold", C.c_void_p)]
 
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -137,6 +137,11 @@ int bnpk_set_option(bnpk_ctx* ctx, const char* name, int64_t value) {
     ctx->sparse_claim = (int)value;
     return BNPK_OK;
   }
+  if (!strcmp(name, "pwm_split")) {
+    if (value < 0 || value > 2) return BNPK_ERR_ARG;
+    ctx->pwm_split = (int)value;
+    return BNPK_OK;
+  }
   if (!strcmp(name, "l1_ring")) {
     if (value < 0 || value > 1) return BNPK_ERR_ARG;
     ctx->l1_ring = (int)value;

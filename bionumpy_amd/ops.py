@@ -506,6 +506,28 @@ class HipOps:
                                       m.ctypes.data_as(C.c_void_p), n_out, ptr(out), self._s()))
         return HArray(dev=out)
 
+    def pwm_rows(self, data, offsets, n_rows, total, matrices, packed, both_strands=False, thresholds=None):
+        """(best float64, position int64, strand uint8 | None, hits int64 | None), each n_motifs * n_rows and motif-major: the
+        best window of every row for every matrix of ``matrices`` (each [code][position]), without a score written.  packed:
+        ``data`` = 2-bit words (bnpk_pwm_rows_packed), else one code byte per symbol (bnpk_pwm_rows_bytes, forward only)"""
+        n_motifs = len(matrices)
+        width = np.array([m.shape[1] for m in matrices], dtype=np.int32)
+        flat = np.concatenate([np.ascontiguousarray(np.asarray(m, dtype=np.float64).T).ravel() for m in matrices])
+        thr = None if thresholds is None else np.ascontiguousarray(thresholds, dtype=np.float64)
+        lib_desc = _native.PwmLibrary(n_motifs, matrices[0].shape[0], width.ctypes.data, flat.ctypes.data,
+                                      None if thr is None else thr.ctypes.data)
+        best, pos = self._empty(n_motifs * n_rows, np.float64), self._empty(n_motifs * n_rows, np.int64)
+        strand = self._empty(n_motifs * n_rows, np.uint8) if packed else None
+        hits = self._empty(n_motifs * n_rows, np.int64) if thr is not None else None
+        src = ptr(data.dev()) if total else None
+        if packed:
+            self._chk(lib.bnpk_pwm_rows_packed(self.ctx, C.byref(lib_desc), src, total, ptr(offsets.dev()), n_rows,
+                                               1 if both_strands else 0, ptr(best), ptr(pos), ptr(strand), ptr(hits), self._s()))
+        else:
+            self._chk(lib.bnpk_pwm_rows_bytes(self.ctx, C.byref(lib_desc), src, total, ptr(offsets.dev()), n_rows, ptr(best),
+                                              ptr(pos), ptr(hits), self._s()))
+        return tuple(None if t is None else HArray(dev=t) for t in (best, pos, strand, hits))
+
     def col_sums_u8(self, data, offsets, n_rows, total, n_cols):
         """(sums int64[n_cols], counts int64[n_cols]) over the columns of ragged uint8 rows"""
         sums, counts = self._empty(n_cols, np.int64), self._empty(n_cols, np.int64)

@@ -7,7 +7,7 @@ from .translate import translate_dna_to_protein
 from .string_matcher import match_string
 from . import string_matcher
 from . import position_weight_matrix
-from .position_weight_matrix import PWM, PositionWeightMatrix, get_motif_scores
+from .position_weight_matrix import PWM, PositionWeightMatrix, get_motif_scores, scan_motifs, MotifScan
 from .count_encoded import count_encoded, EncodedCounts, SparseKmerCounts
 from . import indexing
 from .indexing import KmerIndex, KmerLookup
@@ -16,6 +16,6 @@ from .debruin import DeBruijnGraph, ColoredDeBruijnGraph
 from . import bloom_filter
 from .bloom_filter import BloomFilter
 
-__all__ = ["get_kmers", "count_kmers", "KmerEncoder", "Minimizers", "PositionWeightMatrix", "get_minimizers", "get_reverse_complement", "translate_dna_to_protein", "translate", "match_string", "string_matcher", "PWM", "get_motif_scores", "position_weight_matrix", "count_encoded", "EncodedCounts", "SparseKmerCounts",
+__all__ = ["get_kmers", "count_kmers", "KmerEncoder", "Minimizers", "PositionWeightMatrix", "get_minimizers", "get_reverse_complement", "translate_dna_to_protein", "translate", "match_string", "string_matcher", "PWM", "get_motif_scores", "scan_motifs", "MotifScan", "position_weight_matrix", "count_encoded", "EncodedCounts", "SparseKmerCounts",
            "KmerIndex", "KmerLookup", "indexing", "debruin", "DeBruijnGraph", "ColoredDeBruijnGraph",
            "bloom_filter", "BloomFilter"]

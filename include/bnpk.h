@@ -130,6 +130,7 @@ int bnpk_copy_rates(bnpk_ctx* ctx, const void* d_src, void* d_dst, int64_t bytes
  *                write-combining scatter that lays every round out anew (default; what the other levels use), 1 = one fixed
  *                128-byte line per bucket in LDS, ranks by atomics, nothing laid out or carried (round 6: bit-identical
  *                buckets, 21.7 ms against 17.1 per 6e9 k-mers — kept for the measurements in NOTES.md).  Same buckets.
+ * "pwm_split":   bnpk_pwm_rows_*: who scores a piece of a row (0 = chosen per call, 1 = a lane, 2 = a workgroup).  Same results.
  * Unknown names and values out of range return BNPK_ERR_ARG. */
 int bnpk_set_option(bnpk_ctx* ctx, const char* name, int64_t value);
 
@@ -573,6 +574,48 @@ int bnpk_bloom_rows_packed(bnpk_ctx* ctx, const bnpk_bloom* h_filter, const uint
  * are bit-identical.  h_matrix: width x 4 doubles, [position][code]; d_start_mask = bnpk_kmer_start_mask(k = width). */
 int bnpk_pwm_scores(bnpk_ctx* ctx, const uint64_t* d_packed, const uint64_t* d_start_mask, int64_t n_bases, int width,
                     const double* h_matrix, int64_t n_out, double* d_out, void* stream);
+
+/* ---- a library of position weight matrices per row: best window, where, which strand, how many over a threshold -----------
+ * replaces get_motif_scores(seq, pwm).max(axis=-1) (and argmax, and (scores >= t).sum(axis=-1)) for every PWM of a library
+ * in one call, on both strands if asked, for any alphabet; no score is written (bionumpy/sequence/position_weight_matrix.py:
+ * 86-104, 177-196).  h_lib and what it points at are HOST memory.
+ *   Row r holds the symbols c[0 .. L) = d_offsets[r] .. d_offsets[r + 1] of the flat data (d_offsets[0] == 0,
+ *   d_offsets[n_rows] == n).  Motif m (width W, matrix M laid out [position][code]) scores the window at start p <= L - W
+ *     fwd(p) = ((0.0 + M[0][c[p]]) + M[1][c[p + 1]]) + ... + M[W - 1][c[p + W - 1]]
+ *   in double precision in exactly this order — that of the reference's calculate_scores and of bnpk_pwm_scores, so finite
+ *   results are bit-identical to numpy's.  both_strands != 0 (_packed only: complement = 3 - code) also scores
+ *     rev(p) = ((0.0 + M[0][3 - c[p + W - 1]]) + M[1][3 - c[p + W - 2]]) + ... + M[W - 1][3 - c[p]]
+ *   which is what bnpk_pwm_scores gives on the reverse complement of the row for the window over the same bases.
+ *   Outputs are motif-major, entry [m * n_rows + r]; d_strand and d_hits may be NULL, d_hits needs h_lib->threshold:
+ *     d_best    the largest score of the row's windows (of both strands)
+ *     d_pos     the start, in forward coordinates, of the window that has it, and d_strand its strand (0 forward, 1 reverse);
+ *               among equal scores the forward strand first, then the smaller p: np.argmax(np.concatenate([fwd, rev]))
+ *     d_hits    the (window, strand) pairs with a score >= threshold[m]
+ *   A row with L < W: best = -inf, pos = -1, strand = 0, hits = 0.  A row whose windows all score -inf: best = -inf, pos = 0.
+ *   Matrix entries are finite or -inf (the log 0 of PWM.from_dict); a +inf or NaN in the matrix or the thresholds, a width
+ *   outside 1 .. BNPK_PWM_MAX_WIDTH, n_motifs or alphabet_size outside their ranges are BNPK_ERR_ARG, so no NaN arises.
+ *   n_rows == 0 is BNPK_OK with nothing launched.  _packed: 2-bit bases in the bnpk_gather_encode_dna layout.  _bytes: one
+ *   code < alphabet_size per symbol; any other byte reads no memory outside the motif's table, its window's score is
+ *   unspecified.  Motifs go through BNPK_PWM_GROUP_MOTIFS at a time (fewer where their matrices exceed 4096 entries: wide
+ *   alphabets); the bases are read once per group.  Asynchronous on `stream`; scratch from the ctx arena: 16 bytes per row and
+ *   0.4 per base.  bnpk_set_option "pwm_split": how a piece of 2048 positions of a row is scored — 0 = by the mean row length
+ *   (default), 1 = by one lane, 2 = by one workgroup.  Same results. */
+#define BNPK_PWM_MAX_WIDTH    64
+#define BNPK_PWM_MAX_ALPHABET 32
+#define BNPK_PWM_MAX_MOTIFS   4096
+#define BNPK_PWM_GROUP_MOTIFS 16
+typedef struct {
+  int32_t n_motifs;         /* 1 .. BNPK_PWM_MAX_MOTIFS */
+  int32_t alphabet_size;    /* 4 for _packed, 2 .. BNPK_PWM_MAX_ALPHABET for _bytes */
+  const int32_t* width;     /* HOST, n_motifs entries, each 1 .. BNPK_PWM_MAX_WIDTH */
+  const double* matrix;     /* HOST; motif m at matrix + alphabet_size * (width[0] + .. + width[m-1]), laid out [position][code] */
+  const double* threshold;  /* HOST, n_motifs entries, or NULL */
+} bnpk_pwm_library;
+int bnpk_pwm_rows_packed(bnpk_ctx* ctx, const bnpk_pwm_library* h_lib, const uint64_t* d_packed, int64_t n_bases,
+                         const int64_t* d_offsets, int64_t n_rows, int both_strands, double* d_best, int64_t* d_pos,
+                         uint8_t* d_strand, int64_t* d_hits, void* stream);
+int bnpk_pwm_rows_bytes(bnpk_ctx* ctx, const bnpk_pwm_library* h_lib, const uint8_t* d_codes, int64_t n, const int64_t* d_offsets,
+                        int64_t n_rows, double* d_best, int64_t* d_pos, int64_t* d_hits, void* stream);
 
 /* Same hashes as bnpk_kmers, but never materialised in row order: written exactly once, already partitioned (not
  * stably) by the `bits`-bit digit at bit `shift` (bits <= bnpk_radix_max_bits()) — level 1 of the MSD radix
