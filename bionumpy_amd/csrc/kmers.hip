@@ -745,7 +745,7 @@ int bnpk_kmers_generic(bnpk_ctx* ctx, const uint8_t* d_codes, const int64_t* d_i
 int bnpk_minimizers_generic(bnpk_ctx* ctx, const uint8_t* d_codes, const int64_t* d_in_offsets, const int64_t* d_out_offsets,
                             int64_t n_rows, int64_t n_out, int k, int window_size, int alphabet_size, int64_t* d_out,
                             void* stream) {
-  if (!ctx || k < 1 || window_size < k || alphabet_size < 1 || alphabet_size > 255 || n_rows < 0 || n_out < 0) return BNPK_ERR_ARG;
+  if (!ctx || k < 1 || k > 31 || window_size < k || alphabet_size < 1 || alphabet_size > 255 || n_rows < 0 || n_out < 0) return BNPK_ERR_ARG;
   if (n_out == 0) return BNPK_OK;
   if (!d_codes || !d_in_offsets || !d_out_offsets || !d_out || n_rows == 0) return BNPK_ERR_ARG;
   int64_t blocks = ceil_div(n_out, TILE_OUT);

@@ -211,12 +211,15 @@ int bnpk_multiline_wrap(bnpk_ctx* ctx, const uint8_t* d_names, const int64_t* d_
   hipLaunchKernelGGL(ml_wrap_sizes_kernel, dim3(grid_for(std::min<int64_t>(ceil_div(n_records, 256), 4096))), dim3(256), 0, s,
                      d_name_offsets, d_seq_offsets, n_records, width, d_out_offsets);
   BNPK_CHECK(bnpk_scan_launch(ctx, d_out_offsets, n_records, 1, d_out_offsets, true, (int64_t*)scratch, s));
-  int64_t total = 0;
+  int64_t total = 0, name_bytes = 0, seq_bytes = 0;
   BNPK_HIP(ctx, hipMemcpyAsync(&total, d_out_offsets + n_records, 8, hipMemcpyDeviceToHost, s));
+  BNPK_HIP(ctx, hipMemcpyAsync(&name_bytes, d_name_offsets + n_records, 8, hipMemcpyDeviceToHost, s));
+  BNPK_HIP(ctx, hipMemcpyAsync(&seq_bytes, d_seq_offsets + n_records, 8, hipMemcpyDeviceToHost, s));
   BNPK_HIP(ctx, hipStreamSynchronize(s));
   *h_total = total;
   if (!d_out) return BNPK_OK;                            // (first call: sizes only)
-  if (out_capacity < total || !d_names || !d_seq) return BNPK_ERR_ARG;
+  // (records without any name, or without any sequence, come with an empty buffer — no pointer to read from, and nothing read)
+  if (out_capacity < total || (name_bytes > 0 && !d_names) || (seq_bytes > 0 && !d_seq)) return BNPK_ERR_ARG;
   hipLaunchKernelGGL(ml_wrap_kernel, dim3(grid_for(std::min<int64_t>(ceil_div(total, 256), (int64_t)ctx->compute_units * 32))),
                      dim3(256), 0, s, d_names, d_name_offsets, d_seq, d_seq_offsets, n_records, (const int64_t*)d_out_offsets,
                      total, width, marker, d_out);

@@ -394,7 +394,8 @@ int bnpk_multiline_table(bnpk_ctx* ctx, const uint8_t* d_buf, int64_t size, cons
 /* MultiLineFastaBuffer.from_data (multiline_buffer.py:68-86): record r = marker, its name, '\n', then its sequence
  * (ASCII, rows of d_seq at d_seq_offsets) in lines of `width` letters (n_characters_per_line = 80), every line ended
  * by '\n'.  d_out_offsets (n_records + 1) receives the byte offset of every record; *h_total the size of the text.
- * Call with d_out == NULL to get the sizes, then with a buffer of *h_total bytes. */
+ * Call with d_out == NULL to get the sizes, then with a buffer of *h_total bytes.  A record with an empty sequence is its
+ * header line only; d_names / d_seq may be NULL when no record has a name / a sequence (nothing is read from them). */
 int bnpk_multiline_wrap(bnpk_ctx* ctx, const uint8_t* d_names, const int64_t* d_name_offsets, const uint8_t* d_seq,
                         const int64_t* d_seq_offsets, int64_t n_records, int width, uint8_t marker, int64_t* d_out_offsets,
                         uint8_t* d_out, int64_t out_capacity, int64_t* h_total, void* stream);
@@ -643,7 +644,8 @@ int bnpk_minimizers(bnpk_ctx* ctx, const uint64_t* d_packed, const int64_t* d_in
 /* the same for alphabets that are not 4 letters wide (get_minimizers accepts any AlphabetEncoding,
  * bionumpy/sequence/minimizers.py:48-52): the smallest — as signed int64, which is how numpy's .min compares the wrapped
  * hashes of wide alphabets — of the window_size-k+1 hashes bnpk_kmers_generic gives for the window's k-mers.
- * d_out_offsets = bnpk_row_offsets(lens, window = window_size). */
+ * d_out_offsets = bnpk_row_offsets(lens, window = window_size).  k <= 31, as for bnpk_kmers_generic: a larger k is
+ * BNPK_ERR_ARG in both. */
 int bnpk_minimizers_generic(bnpk_ctx* ctx, const uint8_t* d_codes, const int64_t* d_in_offsets, const int64_t* d_out_offsets,
                             int64_t n_rows, int64_t n_out, int k, int window_size, int alphabet_size, int64_t* d_out,
                             void* stream);

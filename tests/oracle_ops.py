@@ -196,6 +196,10 @@ class OracleOps:
     def pack_codes(self, codes):
         return _pack(codes.host())
 
+    def packed_rows_slice(self, packed, n_bases_in, offsets, first_row, n_rows, first_base, n_bases):
+        codes = _unpack(packed, n_bases_in)[first_base:first_base + n_bases]
+        return _pack(codes), _h(offsets.host()[first_row:first_row + n_rows + 1] - first_base)
+
     def unpack_codes(self, packed, n, to_ascii=False):
         codes = _unpack(packed, n)
         return _h(oracle.decode_dna(codes) if to_ascii else codes)
@@ -247,7 +251,8 @@ class OracleOps:
         for r in range(n_rows):
             row = flat[off[r]:off[r + 1]]
             if row.size:
-                full["sum"][r], full["min"][r], full["max"][r] = row.sum(), row.min(), row.max()
+                with np.errstate(invalid="ignore", over="ignore"):       # (inf - inf, NaN: numpy's answer without its warning)
+                    full["sum"][r], full["min"][r], full["max"][r] = row.sum(), row.min(), row.max()
         return {k: _h(full[k]) for k in want}
 
     def reverse_complement_packed(self, packed, offsets, n_rows, total):
@@ -330,16 +335,21 @@ class OracleOps:
     def count_dense_rows(self, values, offsets, n_rows, n_bins):
         off = offsets.host()
         v = values.host()
-        return _h(np.array([np.bincount(v[off[r]:off[r + 1]], minlength=n_bins) for r in range(n_rows)],
-                           dtype=np.int64).reshape(-1))
+        row = np.repeat(np.arange(n_rows, dtype=np.int64), np.diff(off))
+        ok = (v >= 0) & (v < n_bins)                      # (values outside the bins are not counted: hist_rows_kernel)
+        return _h(np.bincount(row[ok] * n_bins + v[ok], minlength=n_rows * n_bins).astype(np.int64))
 
     def count_weighted(self, values, weights, n, n_rows, value_stride, weight_stride, n_bins):
         v, w = values.host(), weights.host()
-        out = np.zeros((n_rows, n_bins), dtype=w.dtype)
-        for r in range(n_rows):
-            out[r] = np.bincount(v[r * value_stride:r * value_stride + n], weights=w[r * weight_stride:r * weight_stride + n],
-                                 minlength=n_bins).astype(w.dtype)
-        return _h(out.reshape(-1))
+        rows = np.arange(n_rows, dtype=np.int64)[:, None]
+        at = np.arange(n, dtype=np.int64)[None, :]
+        v, w = v[rows * value_stride + at], w[rows * weight_stride + at]
+        if np.any((v < 0) | (v >= n_bins)):
+            raise ValueError("count_encoded: a value outside the alphabet")
+        out = np.zeros(n_rows * n_bins, dtype=w.dtype)    # (int64 weights: wrapping sums, as the kernel's; np.bincount would round them)
+        with np.errstate(invalid="ignore"):
+            np.add.at(out, (rows * n_bins + v).reshape(-1), w.reshape(-1))
+        return _h(out)
 
     def count_sparse(self, values, key_bits=62, consume=False, partition=None, key_range=None, fast=True, skew=1.0, dest=None):
         k, c = oracle.count_sparse(values.host())

@@ -982,6 +982,25 @@ def test_count_encoded_with_weights(bnp):
         bnp.count_encoded(bnp.as_encoded_array(["ACGT", "AC"], bnp.DNAEncoding), weights=np.ones(4))
 
 
+def test_count_encoded_with_weights_over_more_rows_than_one_launch(bnp):
+    # count_encoded.py:176-187 with more rows than one launch of bnpk_count_weighted takes (32 768: three trips of the loop in
+    # sequence/count_encoded.py::_count_weighted), a different row on either side of the cut; against oracle.count_weighted
+    rng = np.random.default_rng(12)
+    mat = rng.integers(0, 4, size=(70_000, 3))
+    mat[32_767], mat[32_768] = [0, 0, 1], [3, 2, 2]
+    letters = np.frombuffer(b"ACGT", dtype=np.uint8)[mat]
+    rows = bnp.as_encoded_array([r.tobytes().decode() for r in letters], bnp.DNAEncoding)
+    w1 = np.array([1, 10, 100])
+    got, expect = bnp.count_encoded(rows, weights=w1).counts, oracle.count_weighted(mat, w1, 4)
+    assert got.shape == (70_000, 4) and got.dtype == np.float64 and np.array_equal(got, expect)
+    assert got[32_767].tolist() == [11, 100, 0, 0] and got[32_768].tolist() == [0, 0, 110, 1]
+    # 2-D integer weights, one histogram per row of theirs, over five flat values
+    flat = bnp.as_encoded_array("GATTC", bnp.DNAEncoding)
+    w2 = rng.integers(-50, 50, size=(40_000, 5))
+    got, expect = bnp.count_encoded(flat, weights=w2).counts, oracle.count_weighted(np.array([2, 0, 3, 3, 1]), w2, 4)
+    assert got.shape == (40_000, 4) and np.issubdtype(got.dtype, np.integer) and np.array_equal(got, expect)
+
+
 def test_minimizers_of_any_alphabet(bnp):
     # get_minimizers accepts any AlphabetEncoding (sequence/minimizers.py:48-52): the rolling hash of KmerEncoder
     # (codes . alphabet_size ** arange(k), wrapping int64) and the smallest of each window as numpy compares int64

@@ -54,6 +54,48 @@ def test_bad_arguments(env):
     assert lib.bnpk_strerror(ERR_RANGE).decode() == "size out of supported range"
 
 
+def test_generic_minimizers_refuse_k_beyond_31_like_the_generic_kmers(env):
+    """bnpk_kmers_generic and bnpk_minimizers_generic take the same k (1..31): the windows' minima are minima of the hashes the
+    former gives.  The host asks the same of get_minimizers and get_kmers; KmerEncoder hands its k to the library."""
+    lib, dev, ptr, torch = env
+    codes = torch.ones(64, dtype=torch.uint8, device="cuda")
+    in_off = torch.tensor([0, 64], dtype=torch.int64, device="cuda")
+    out = torch.zeros(64, dtype=torch.int64, device="cuda")
+    for k, window, status in ((31, 31, OK), (31, 40, OK), (32, 32, ERR_ARG), (32, 40, ERR_ARG), (40, 40, ERR_ARG)):
+        out_off = torch.tensor([0, 64 - window + 1], dtype=torch.int64, device="cuda")
+        assert lib.bnpk_minimizers_generic(dev.ctx, ptr(codes), ptr(in_off), ptr(out_off), 1, 64 - window + 1, k, window, 2,
+                                           ptr(out), None) == status, (k, window)
+    out_off = torch.tensor([0, 64 - 31 + 1], dtype=torch.int64, device="cuda")
+    assert lib.bnpk_kmers_generic(dev.ctx, ptr(codes), ptr(in_off), ptr(out_off), 1, 34, 31, 2, ptr(out), None) == OK
+    torch.cuda.synchronize()
+    assert out[:34].tolist() == [(1 << 31) - 1] * 34                  # 31 ones of a 2-letter alphabet
+    import bionumpy_amd as bnp
+    from bionumpy_amd import ops as ops_mod
+    from bionumpy_amd._native import BnpkError
+    from bionumpy_amd.sequence.kmers import KmerEncoder
+    ops_mod.set_ops(None)
+    two = bnp.AlphabetEncoding("AB")
+    seq = bnp.as_encoded_array("AB" * 40, two)
+    with pytest.raises(AssertionError):
+        bnp.get_minimizers(seq, 40, 50)
+    with pytest.raises(AssertionError):
+        bnp.get_kmers(seq, 40)
+    with pytest.raises(BnpkError):
+        KmerEncoder(40, two).rolling_window(seq)
+
+
+def test_count_weighted_row_limits(env):
+    """one histogram per blockIdx.y: 65 535 rows at the most per call (the host cuts its rows into launches of 32 768)"""
+    lib, dev, ptr, torch = env
+    values = torch.zeros(16, dtype=torch.int64, device="cuda")
+    hist = torch.zeros(16, dtype=torch.int64, device="cuda")
+    bad = C.c_int(5)
+    assert lib.bnpk_count_weighted(dev.ctx, ptr(values), ptr(values), 0, 1, 65_536, 0, 0, 1, ptr(hist), C.byref(bad), None) == ERR_RANGE
+    assert lib.bnpk_count_weighted(dev.ctx, ptr(values), ptr(values), 0, 1, 0, 0, 0, 1, ptr(hist), C.byref(bad), None) == ERR_ARG
+    torch.cuda.synchronize()
+    assert torch.count_nonzero(hist).item() == 0                     # untouched
+
+
 def test_out_of_memory_is_a_status(env):
     lib, dev, ptr, torch = env
     p = C.c_void_p()

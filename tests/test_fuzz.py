@@ -42,11 +42,20 @@ def _rounds(ops, seed, make_cases, least=2):
 
 def test_byte_movers_and_window_kernels_at_random_shapes(ops):
     """gather + encode, reverse complement (the shape that found the miscompile is one of these), row reductions, joins,
-    window matches — up to 150 000 rows and tens of millions of elements"""
+    window matches — up to 150 000 rows and tens of millions of elements; the wide reductions, generic k-mers and minimizers,
+    weighted and per-row histograms of tests/test_wide_generic_parity.py at a few million elements"""
+    import test_wide_generic_parity as W
+
     def cases(T, rng):
         seed = int(rng.integers(10, 1 << 30))
         rows = int(rng.choice([1, 2, 17, 300, 5000, 40000, 150000]))
-        return [(T.test_gather_encode_rows_between_other_text, (seed, max(rows, 8), int(rng.integers(1, 60)), int(rng.integers(61, 400)), bool(rng.integers(0, 2)))),
+        k = int(rng.choice([1, 3, 15, 31]))
+        wide = [(W.test_row_reduce_wide_random, (seed, min(rows, 5000), int(rng.choice([1, 7, 160, 3000])))),
+                (W.test_generic_kmers_and_minimizers_random, (seed, min(rows, 3000), int(rng.choice([5, 60, 300])),
+                                                              int(rng.choice([2, 5, 20, 255])), k, k + int(rng.choice([0, 1, 9])))),
+                (W.test_count_weighted_random, (seed, rows, int(rng.choice([1, 40, 300, 5000])))),
+                (W.test_count_dense_rows_random, (seed, min(rows, 5000), int(rng.choice([1, 50, 151, 3000]))))]
+        return wide + [(T.test_gather_encode_rows_between_other_text, (seed, max(rows, 8), int(rng.integers(1, 60)), int(rng.integers(61, 400)), bool(rng.integers(0, 2)))),
                 (T.test_gather_encode_and_kmers, (seed, rows, int(rng.choice([3, 40, 200, 1000])))),
                 (T.test_reverse_complement_kernels, (seed, rows, int(rng.choice([1, 20, 151, 700])))),
                 (T.test_row_reductions, (seed, rows, int(rng.choice([1, 7, 160, 3000])))),
