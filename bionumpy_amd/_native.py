@@ -140,6 +140,9 @@ SIGNATURES = {
     "bnpk_pwm_scores": (_int, [_p, _p, _p, _i64, _int, _p, _i64, _p, _p]),
     "bnpk_pwm_rows_packed": (_int, [_p, _p, _p, _i64, _p, _i64, _int, _p, _p, _p, _p, _p]),
     "bnpk_pwm_rows_bytes": (_int, [_p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p]),
+    "bnpk_approx_rows_packed": (_int, [_p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p]),
+    "bnpk_approx_rows_bytes": (_int, [_p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p]),
+    "bnpk_approx_trim_lens": (_int, [_p, _p, _p, _i64, _p, _p]),
     "bnpk_kmers_partition": (_int, [_p, _p, _p, _i64, _int, _int, _int, _int, _p, _p, _p]),
     "bnpk_minimizers": (_int, [_p, _p, _p, _p, _i64, _i64, _int, _int, _p, _p]),
     "bnpk_count_bytes": (_int, [_p, _p, _i64, _int, _p, _p]),
@@ -200,6 +203,15 @@ class PwmLibrary(C.Structure):
     """bnpk_pwm_library of include/bnpk.h: widths, matrices ([position][code], one after the other) and thresholds on the host"""
     _fields_ = [("n_motifs", C.c_int32), ("alphabet_size", C.c_int32), ("width", C.c_void_p), ("matrix", C.c_void_p),
                 ("threshold", C.c_void_p)]
+
+
+APPROX_MAX_LEN, APPROX_MAX_PATTERNS, APPROX_MAX_ALPHABET = 64, 1024, 32
+
+
+class ApproxLibrary(C.Structure):
+    """bnpk_approx_library of include/bnpk.h: lengths, error budgets, overhangs and acceptance masks on the host"""
+    _fields_ = [("n_patterns", C.c_int32), ("alphabet_size", C.c_int32), ("m", C.c_void_p), ("max_errors", C.c_void_p),
+                ("min_overlap", C.c_void_p), ("eq", C.c_void_p)]
 
 
 for _name, (_res, _args) in SIGNATURES.items():

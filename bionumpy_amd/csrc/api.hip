@@ -142,6 +142,11 @@ int bnpk_set_option(bnpk_ctx* ctx, const char* name, int64_t value) {
     ctx->pwm_split = (int)value;
     return BNPK_OK;
   }
+  if (!strcmp(name, "approx_piece")) {
+    if (value != 0 && (value < 256 || value > (1 << 30) || (value & (value - 1)))) return BNPK_ERR_ARG;
+    ctx->approx_piece = (int)value;
+    return BNPK_OK;
+  }
   if (!strcmp(name, "l1_ring")) {
     if (value < 0 || value > 1) return BNPK_ERR_ARG;
     ctx->l1_ring = (int)value;

@@ -57,6 +57,7 @@ struct bnpk_ctx {
   int index_pairs = 1;           // sparse.hip: bnpk_index_build as one partition of (k-mer, row) words where the rows fit (0: always by ranks)
   int sparse_claim = 1;          // sparse.hip: may bnpk_count_sparse run its last level as the claiming level (0: never — tests, experiments)
   int pwm_split = 0;             // pwm_rows.hip: a piece of a row goes to 0 = what the mean row length says, 1 = one lane, 2 = one workgroup
+  int approx_piece = 0;          // approx.hip: positions of a row per piece (0 = chosen per call; else a power of two >= 256)
   int l1_ring = 0;               // radix.hip: the fused first level's scatter — 0 = rp_scatter_kernel, 1 = rp_ring_kernel (one fixed line per bucket: round 6, measured slower)
 };
 

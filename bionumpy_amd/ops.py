@@ -528,6 +528,29 @@ class HipOps:
                                               ptr(pos), ptr(hits), self._s()))
         return tuple(None if t is None else HArray(dev=t) for t in (best, pos, strand, hits))
 
+    def approx_rows(self, data, offsets, n_rows, total, masks, max_errors, min_overlap, lengths, packed, count_hits=False):
+        """(dist uint8, start int64, end int64, overlap uint8, hits int64 | None), each n_patterns * n_rows and pattern-major:
+        the best approximate occurrence of every pattern in every row (bnpk_approx_rows_packed on 2-bit words, else
+        bnpk_approx_rows_bytes on code bytes).  masks: uint64 [pattern][code], bit i = position i accepts the code"""
+        masks = np.ascontiguousarray(masks, dtype=np.uint64)
+        n_patterns, alphabet_size = masks.shape
+        m, k, o = (np.ascontiguousarray(np.broadcast_to(x, (n_patterns,)), dtype=np.int32) for x in (lengths, max_errors, min_overlap))
+        desc = _native.ApproxLibrary(n_patterns, alphabet_size, m.ctypes.data, k.ctypes.data, o.ctypes.data, masks.ctypes.data)
+        n_out = n_patterns * n_rows
+        dist, overlap = self._empty(n_out, np.uint8), self._empty(n_out, np.uint8)
+        start, end = self._empty(n_out, np.int64), self._empty(n_out, np.int64)
+        hits = self._empty(n_out, np.int64) if count_hits else None
+        call = lib.bnpk_approx_rows_packed if packed else lib.bnpk_approx_rows_bytes
+        self._chk(call(self.ctx, C.byref(desc), ptr(data.dev()) if total else None, total, ptr(offsets.dev()), n_rows, ptr(dist),
+                       ptr(start), ptr(end), ptr(overlap), ptr(hits), self._s()))
+        return tuple(None if t is None else HArray(dev=t) for t in (dist, start, end, overlap, hits))
+
+    def approx_trim_lens(self, start, lens, n_rows):
+        """int64 per row: start where it is >= 0, else the row's length (bnpk_approx_trim_lens)"""
+        out = self._empty(n_rows, np.int64)
+        self._chk(lib.bnpk_approx_trim_lens(self.ctx, ptr(start.dev()), ptr(lens.dev()), n_rows, ptr(out), self._s()))
+        return HArray(dev=out)
+
     def col_sums_u8(self, data, offsets, n_rows, total, n_cols):
         """(sums int64[n_cols], counts int64[n_cols]) over the columns of ragged uint8 rows"""
         sums, counts = self._empty(n_cols, np.int64), self._empty(n_cols, np.int64)

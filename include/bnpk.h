@@ -131,6 +131,7 @@ int bnpk_copy_rates(bnpk_ctx* ctx, const void* d_src, void* d_dst, int64_t bytes
  *                128-byte line per bucket in LDS, ranks by atomics, nothing laid out or carried (round 6: bit-identical
  *                buckets, 21.7 ms against 17.1 per 6e9 k-mers — kept for the measurements in NOTES.md).  Same buckets.
  * "pwm_split":   bnpk_pwm_rows_*: who scores a piece of a row (0 = chosen per call, 1 = a lane, 2 = a workgroup).  Same results.
+ * "approx_piece": bnpk_approx_rows_*: the positions of a row per piece (0 = chosen per call, else a power of two >= 256).  Same results.
  * Unknown names and values out of range return BNPK_ERR_ARG. */
 int bnpk_set_option(bnpk_ctx* ctx, const char* name, int64_t value);
 
@@ -617,6 +618,52 @@ int bnpk_pwm_rows_packed(bnpk_ctx* ctx, const bnpk_pwm_library* h_lib, const uin
                          uint8_t* d_strand, int64_t* d_hits, void* stream);
 int bnpk_pwm_rows_bytes(bnpk_ctx* ctx, const bnpk_pwm_library* h_lib, const uint8_t* d_codes, int64_t n, const int64_t* d_offsets,
                         int64_t n_rows, double* d_best, int64_t* d_pos, int64_t* d_hits, void* stream);
+
+/* ---- approximate search: a library of patterns per row under the edit distance, and where to cut an adapter ----------------
+ * h_lib and what it points at are HOST memory.  Row r holds the symbols c[0 .. L) = d_offsets[r] .. d_offsets[r + 1] of the
+ * flat data (d_offsets[0] == 0, d_offsets[n_rows] == n).
+ *   Pattern p has m positions, 1 <= m <= BNPK_APPROX_MAX_LEN, given as acceptance masks: bit i of eq[a] is set iff position i
+ *   accepts code a (letters, wildcards and classes alike), and max_errors k, 0 <= k < m.  With unit costs for a
+ *   substitution, an insertion and a deletion,
+ *     D[i][j] = min over 0 <= s <= j of ed(P[0:i], c[s:j])          (semi-global: free start in the row, D[i][0] = i)
+ *   Outputs are pattern-major, entry [p * n_rows + r]; d_hits may be NULL:
+ *     d_dist (uint8)   min over 0 <= j <= L of D[m][j]; never more than m
+ *     d_end            the smallest j that attains it (exclusive end)
+ *     found iff dist <= k.  Then d_overlap (uint8) = m and d_start = end - t for the smallest t with
+ *                      ed(P, c[end - t : end]) == dist: the shortest match that ends there (a t <= m + dist exists)
+ *     not found and min_overlap o > 0: the pattern may run off the row's end.  With the largest i in [o, m - 1] such that
+ *                      D[i][L] <= (k * i) / m (integer division), if there is one: dist = D[i][L], end = L, overlap = i and
+ *                      start = L - t for the smallest t with ed(P[0:i], c[L - t : L]) == dist
+ *     otherwise        dist stays the minimum, start = end = -1, overlap = 0
+ *     d_hits           the number of j in 1 .. L with D[m][j] <= k
+ *   A row of no symbols is a row like any other: dist = m, not found.
+ *   BNPK_ERR_ARG: m outside 1 .. BNPK_APPROX_MAX_LEN, k >= m, min_overlap >= m (or negative), n_patterns outside
+ *   1 .. BNPK_APPROX_MAX_PATTERNS, alphabet_size outside its range, a mask with bits at or above m.  n_rows == 0 is BNPK_OK
+ *   with nothing launched.  _packed: 2-bit bases in the bnpk_gather_encode_dna layout, 4 masks per pattern.  _bytes: one
+ *   code < alphabet_size per symbol, alphabet_size masks per pattern; any other byte is accepted by no position and reads no
+ *   memory outside the masks.  Asynchronous on `stream` (the library is copied before the call returns); scratch from the
+ *   ctx arena: 16 bytes per row and 512 per piece length of symbols (at most 2 per symbol, 128 MiB at most).  Long rows are searched in pieces (bnpk_set_option
+ *   "approx_piece"), with the same results for every piece length.
+ * bnpk_approx_trim_lens: d_out[r] = d_start[r] >= 0 ? min(d_start[r], d_lens[r]) : d_lens[r] — what a row keeps when it is
+ *   cut where its adapter starts. */
+#define BNPK_APPROX_MAX_LEN      64
+#define BNPK_APPROX_MAX_PATTERNS 1024
+#define BNPK_APPROX_MAX_ALPHABET 32
+typedef struct {
+  int32_t n_patterns;          /* 1 .. BNPK_APPROX_MAX_PATTERNS */
+  int32_t alphabet_size;       /* 4 for _packed, 1 .. BNPK_APPROX_MAX_ALPHABET for _bytes */
+  const int32_t* m;            /* HOST, n_patterns entries */
+  const int32_t* max_errors;   /* HOST, n_patterns entries */
+  const int32_t* min_overlap;  /* HOST, n_patterns entries; 0 = the pattern must lie in the row whole */
+  const uint64_t* eq;          /* HOST; pattern p's masks at eq + alphabet_size * p */
+} bnpk_approx_library;
+int bnpk_approx_rows_packed(bnpk_ctx* ctx, const bnpk_approx_library* h_lib, const uint64_t* d_packed, int64_t n_bases,
+                            const int64_t* d_offsets, int64_t n_rows, uint8_t* d_dist, int64_t* d_start, int64_t* d_end,
+                            uint8_t* d_overlap, int64_t* d_hits, void* stream);
+int bnpk_approx_rows_bytes(bnpk_ctx* ctx, const bnpk_approx_library* h_lib, const uint8_t* d_codes, int64_t n,
+                           const int64_t* d_offsets, int64_t n_rows, uint8_t* d_dist, int64_t* d_start, int64_t* d_end,
+                           uint8_t* d_overlap, int64_t* d_hits, void* stream);
+int bnpk_approx_trim_lens(bnpk_ctx* ctx, const int64_t* d_start, const int64_t* d_lens, int64_t n_rows, int64_t* d_out, void* stream);
 
 /* Same hashes as bnpk_kmers, but never materialised in row order: written exactly once, already partitioned (not
  * stably) by the `bits`-bit digit at bit `shift` (bits <= bnpk_radix_max_bits()) — level 1 of the MSD radix
