@@ -143,6 +143,8 @@ SIGNATURES = {
     "bnpk_approx_rows_packed": (_int, [_p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p]),
     "bnpk_approx_rows_bytes": (_int, [_p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _p, _p]),
     "bnpk_approx_trim_lens": (_int, [_p, _p, _p, _i64, _p, _p]),
+    "bnpk_demux_rows_packed": (_int, [_p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p]),
+    "bnpk_demux_rows_bytes": (_int, [_p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p]),
     "bnpk_kmers_partition": (_int, [_p, _p, _p, _i64, _int, _int, _int, _int, _p, _p, _p]),
     "bnpk_minimizers": (_int, [_p, _p, _p, _p, _i64, _i64, _int, _int, _p, _p]),
     "bnpk_count_bytes": (_int, [_p, _p, _i64, _int, _p, _p]),
@@ -212,6 +214,15 @@ class ApproxLibrary(C.Structure):
     """bnpk_approx_library of include/bnpk.h: lengths, error budgets, overhangs and acceptance masks on the host"""
     _fields_ = [("n_patterns", C.c_int32), ("alphabet_size", C.c_int32), ("m", C.c_void_p), ("max_errors", C.c_void_p),
                 ("min_overlap", C.c_void_p), ("eq", C.c_void_p)]
+
+
+DEMUX_MAX_LEN, DEMUX_MAX_BARCODES, DEMUX_NONE = 32, 1 << 20, 255
+
+
+class DemuxLibrary(C.Structure):
+    """bnpk_demux_library of include/bnpk.h: equal-length barcodes as codes on the host, the window and the acceptance rule"""
+    _fields_ = [("n_barcodes", C.c_int32), ("length", C.c_int32), ("start", C.c_int32), ("max_mismatches", C.c_int32),
+                ("min_delta", C.c_int32), ("codes", C.c_void_p)]
 
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -273,14 +273,17 @@ int bnpk_vec_ratio_rows(bnpk_ctx* ctx, const int64_t* d_sums, const int64_t* d_o
 
 int bnpk_vec_compare(bnpk_ctx* ctx, const void* d_x, int64_t n, int dtype, int op, double scalar_f64, int64_t scalar_i64,
                      uint8_t* d_out, void* stream) {
-  if (!ctx || n < 0 || dtype < 0 || dtype > 2 || op < 0 || op > 5 || (n > 0 && (!d_x || !d_out))) return BNPK_ERR_ARG;
+  if (!ctx || n < 0 || dtype < 0 || dtype > 3 || op < 0 || op > 5 || (n > 0 && (!d_x || !d_out))) return BNPK_ERR_ARG;
   if (n == 0) return BNPK_OK;
   hipStream_t s = (hipStream_t)stream;
   bnpk_timer t(ctx, "vec_compare", s);
   const dim3 grid(grid_for(ceil_div(n, 256))), block(256);
   if (dtype == 0) hipLaunchKernelGGL((vec_compare_kernel<double>), grid, block, 0, s, (const double*)d_x, n, op, scalar_f64, d_out);
   else if (dtype == 1) hipLaunchKernelGGL((vec_compare_kernel<int64_t>), grid, block, 0, s, (const int64_t*)d_x, n, op, scalar_i64, d_out);
-  else {
+  else if (dtype == 3) {
+    if (scalar_i64 < INT32_MIN || scalar_i64 > INT32_MAX) return BNPK_ERR_ARG;
+    hipLaunchKernelGGL((vec_compare_kernel<int32_t>), grid, block, 0, s, (const int32_t*)d_x, n, op, (int32_t)scalar_i64, d_out);
+  } else {
     if (scalar_i64 < 0 || scalar_i64 > 255) return BNPK_ERR_ARG;     // (the caller folds comparisons that no uint8 can decide)
     hipLaunchKernelGGL((vec_compare_kernel<uint8_t>), grid, block, 0, s, (const uint8_t*)d_x, n, op, (uint8_t)scalar_i64, d_out);
   }

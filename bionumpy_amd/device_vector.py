@@ -102,7 +102,7 @@ class DeviceVector:
     # -- comparisons with a scalar: a mask on the device ---------------------------------------------------------
     def _compare(self, name, other):
         if isinstance(other, (int, float, np.integer, np.floating)) and not isinstance(other, bool) and \
-                self._dtype in (np.float64, np.int64, np.uint8):
+                self._dtype in (np.float64, np.int64, np.uint8, np.int32):
             if self._dtype == np.float64:
                 on_device = not isinstance(other, (int, np.integer)) or abs(int(other)) <= (1 << 53)   # (exact as a double)
             else:
@@ -113,7 +113,8 @@ class DeviceVector:
                 else:
                     whole = math.isfinite(float(other)) and float(other) == int(other)
                     value = int(other) if whole else 0
-                lo, hi = (0, 255) if self._dtype == np.uint8 else (-(1 << 63), (1 << 63) - 1)
+                lo, hi = {np.dtype(np.uint8): (0, 255), np.dtype(np.int32): (-(1 << 31), (1 << 31) - 1)}.get(
+                    self._dtype, (-(1 << 63), (1 << 63) - 1))
                 on_device = whole and lo <= value <= hi
             if on_device:
                 return DeviceVector(get_ops().vec_compare(self._data, _OPS[name], other), np.bool_)

@@ -551,6 +551,19 @@ class HipOps:
         self._chk(lib.bnpk_approx_trim_lens(self.ctx, ptr(start.dev()), ptr(lens.dev()), n_rows, ptr(out), self._s()))
         return HArray(dev=out)
 
+    def demux_rows(self, data, offsets, n_rows, total, codes, start, max_mismatches, min_delta, packed):
+        """(index int32, dist uint8, second uint8), one entry per row: the nearest barcode of ``codes`` (uint8
+        [barcode][position], each < 4) to the window [start, start + L) of every row under the Hamming distance
+        (bnpk_demux_rows_packed on 2-bit words, else bnpk_demux_rows_bytes on code bytes)"""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        n_barcodes, length = codes.shape
+        desc = _native.DemuxLibrary(n_barcodes, length, start, max_mismatches, min_delta, codes.ctypes.data)
+        index, dist, second = self._empty(n_rows, np.int32), self._empty(n_rows, np.uint8), self._empty(n_rows, np.uint8)
+        call = lib.bnpk_demux_rows_packed if packed else lib.bnpk_demux_rows_bytes
+        self._chk(call(self.ctx, C.byref(desc), ptr(data.dev()) if total else None, total, ptr(offsets.dev()), n_rows, ptr(index),
+                       ptr(dist), ptr(second), self._s()))
+        return tuple(HArray(dev=t) for t in (index, dist, second))
+
     def col_sums_u8(self, data, offsets, n_rows, total, n_cols):
         """(sums int64[n_cols], counts int64[n_cols]) over the columns of ragged uint8 rows"""
         sums, counts = self._empty(n_cols, np.int64), self._empty(n_cols, np.int64)
@@ -618,9 +631,9 @@ class HipOps:
         return HArray(dev=out)
 
     def vec_compare(self, x, op, scalar):
-        """x OP scalar as a 0/1 uint8 mask; x float64 / int64 / uint8, op one of < <= > >= == !="""
+        """x OP scalar as a 0/1 uint8 mask; x float64 / int64 / uint8 / int32, op one of < <= > >= == !="""
         code = {"<": 0, "<=": 1, ">": 2, ">=": 3, "==": 4, "!=": 5}[op]
-        dtype = {np.dtype(np.float64): 0, np.dtype(np.int64): 1, np.dtype(np.uint8): 2}[np.dtype(x.dtype)]
+        dtype = {np.dtype(np.float64): 0, np.dtype(np.int64): 1, np.dtype(np.uint8): 2, np.dtype(np.int32): 3}[np.dtype(x.dtype)]
         out = self._empty(x.size, np.uint8)
         self._chk(lib.bnpk_vec_compare(self.ctx, ptr(x.dev()), x.size, dtype, code, float(scalar) if dtype == 0 else 0.0,
                                        int(scalar) if dtype != 0 else 0, ptr(out), self._s()))

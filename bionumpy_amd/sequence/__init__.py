@@ -17,7 +17,10 @@ from . import bloom_filter
 from .bloom_filter import BloomFilter
 from . import approximate
 from .approximate import find_approximate, trim_adapters, ApproxScan
+from . import barcodes
+from .barcodes import assign_barcodes, BarcodeAssignment
 
 __all__ = ["get_kmers", "count_kmers", "KmerEncoder", "Minimizers", "PositionWeightMatrix", "get_minimizers", "get_reverse_complement", "translate_dna_to_protein", "translate", "match_string", "string_matcher", "PWM", "get_motif_scores", "scan_motifs", "MotifScan", "position_weight_matrix", "count_encoded", "EncodedCounts", "SparseKmerCounts",
            "KmerIndex", "KmerLookup", "indexing", "debruin", "DeBruijnGraph", "ColoredDeBruijnGraph",
-           "bloom_filter", "BloomFilter", "approximate", "find_approximate", "trim_adapters", "ApproxScan"]
+           "bloom_filter", "BloomFilter", "approximate", "find_approximate", "trim_adapters", "ApproxScan",
+           "barcodes", "assign_barcodes", "BarcodeAssignment"]

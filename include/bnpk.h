@@ -342,7 +342,7 @@ int bnpk_row_reduce_wide(bnpk_ctx* ctx, const void* d_data, int is_f64, const in
 /* Element-wise helpers of the read filters (scripts/small_example.py:36-46: `np.mean(chunk.quality, axis=1) > 30`,
  * `mask[::3] = False`, `mask1 & mask2`, `chunk[mask]`) on per-row values that stay in HBM (bionumpy_amd/device_vector.py):
  *   bnpk_vec_ratio_rows  d_out[i] = (double)d_sums[i] / (double)(d_offsets[i+1] - d_offsets[i])   — np.mean(ragged, axis=-1)
- *   bnpk_vec_compare     d_out[i] = d_x[i] OP scalar as 0/1; dtype 0 = float64 (scalar_f64), 1 = int64, 2 = uint8
+ *   bnpk_vec_compare     d_out[i] = d_x[i] OP scalar as 0/1; dtype 0 = float64 (scalar_f64), 1 = int64, 2 = uint8, 3 = int32
  *                        (scalar_i64); op 0 <, 1 <=, 2 >, 3 >=, 4 ==, 5 != (IEEE: comparisons with nan are false, != true)
  *   bnpk_mask_logic      d_out = d_a AND / OR / XOR d_b (op 0 / 1 / 2) or NOT d_a (op 3, d_b unused); masks are 0/1 bytes
  *   bnpk_mask_fill       d_mask[start + i * step] = value for i < count   — mask[start:stop:step] = value
@@ -664,6 +664,39 @@ int bnpk_approx_rows_bytes(bnpk_ctx* ctx, const bnpk_approx_library* h_lib, cons
                            const int64_t* d_offsets, int64_t n_rows, uint8_t* d_dist, int64_t* d_start, int64_t* d_end,
                            uint8_t* d_overlap, int64_t* d_hits, void* stream);
 int bnpk_approx_trim_lens(bnpk_ctx* ctx, const int64_t* d_start, const int64_t* d_lens, int64_t n_rows, int64_t* d_out, void* stream);
+
+/* ---- barcode assignment (demultiplexing): the nearest barcode of a library per row under the Hamming distance --------------
+ * h_lib and what it points at are HOST memory.  Row r holds the symbols c[0 .. len) = d_offsets[r] .. d_offsets[r + 1] of the
+ * flat data (d_offsets[0] == 0, d_offsets[n_rows] == n).  The library holds n_barcodes barcodes of L codes < 4 each.
+ *   A row with len >= start + L has the window w = c[start .. start + L) and d[b] = #{i : w[i] != codes[b][i]}; in _bytes a
+ *   code >= 4 (N, or anything else) differs from every letter.  One entry per row:
+ *     best              the smallest b that attains min d
+ *     d_dist (uint8)    d[best]
+ *     d_second (uint8)  min over b != best of d[b]; BNPK_DEMUX_NONE when n_barcodes == 1
+ *     d_index (int32)   best if d_dist <= max_mismatches and (n_barcodes == 1 or d_second - d_dist >= min_delta), else -1
+ *   A shorter row, an empty one included: d_index = -1, d_dist = d_second = BNPK_DEMUX_NONE; nothing outside the row is read.
+ *   BNPK_ERR_ARG: n_barcodes outside 1 .. BNPK_DEMUX_MAX_BARCODES, length outside 1 .. BNPK_DEMUX_MAX_LEN, start < 0,
+ *   max_mismatches outside 0 .. length, min_delta < 0, a code >= 4 in the library.  n_rows == 0 is BNPK_OK with nothing
+ *   launched; the library is still checked.  _packed: 2-bit bases in the bnpk_gather_encode_dna layout.  _bytes: one code per
+ *   symbol.  Asynchronous on `stream` (the library is copied before the call returns); scratch from the ctx arena: 1024 bytes
+ *   per 16 barcodes (2048 where length > 16), rounded up to 128 barcodes, and a byte per code: 160 MiB for 2^20 barcodes of
+ *   32.  Equal barcodes are no error here: the larger index of a pair is never assigned. */
+#define BNPK_DEMUX_MAX_LEN       32
+#define BNPK_DEMUX_MAX_BARCODES  (1 << 20)
+#define BNPK_DEMUX_NONE          255
+typedef struct {
+  int32_t n_barcodes;      /* 1 .. BNPK_DEMUX_MAX_BARCODES */
+  int32_t length;          /* L: 1 .. BNPK_DEMUX_MAX_LEN, the same for every barcode */
+  int32_t start;           /* >= 0: the window is symbols [start, start + L) of every row */
+  int32_t max_mismatches;  /* k: 0 .. L */
+  int32_t min_delta;       /* >= 0: how much farther the runner-up must be */
+  const uint8_t* codes;    /* HOST, n_barcodes * L codes, each < 4 */
+} bnpk_demux_library;
+int bnpk_demux_rows_packed(bnpk_ctx* ctx, const bnpk_demux_library* h_lib, const uint64_t* d_packed, int64_t n_bases,
+                           const int64_t* d_offsets, int64_t n_rows, int32_t* d_index, uint8_t* d_dist, uint8_t* d_second,
+                           void* stream);
+int bnpk_demux_rows_bytes(bnpk_ctx* ctx, const bnpk_demux_library* h_lib, const uint8_t* d_codes, int64_t n, const int64_t* d_offsets,
+                          int64_t n_rows, int32_t* d_index, uint8_t* d_dist, uint8_t* d_second, void* stream);
 
 /* Same hashes as bnpk_kmers, but never materialised in row order: written exactly once, already partitioned (not
  * stably) by the `bits`-bit digit at bit `shift` (bits <= bnpk_radix_max_bits()) — level 1 of the MSD radix
