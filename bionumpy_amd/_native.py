@@ -145,6 +145,11 @@ SIGNATURES = {
     "bnpk_approx_trim_lens": (_int, [_p, _p, _p, _i64, _p, _p]),
     "bnpk_demux_rows_packed": (_int, [_p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p]),
     "bnpk_demux_rows_bytes": (_int, [_p, _p, _p, _i64, _p, _i64, _p, _p, _p, _p]),
+    "bnpk_mates_overlap_packed": (_int, [_p, _p, _p, _i64, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _p]),
+    "bnpk_mates_overlap_bytes": (_int, [_p, _p, _p, _i64, _p, _p, _i64, _p, _i64, _p, _p, _p, _p, _p]),
+    "bnpk_mates_lengths": (_int, [_p, _p, _i64, _p, _p]),
+    "bnpk_mates_merge_packed": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p]),
+    "bnpk_mates_merge_bytes": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p]),
     "bnpk_kmers_partition": (_int, [_p, _p, _p, _i64, _int, _int, _int, _int, _p, _p, _p]),
     "bnpk_minimizers": (_int, [_p, _p, _p, _p, _i64, _i64, _int, _int, _p, _p]),
     "bnpk_count_bytes": (_int, [_p, _p, _i64, _int, _p, _p]),
@@ -223,6 +228,15 @@ class DemuxLibrary(C.Structure):
     """bnpk_demux_library of include/bnpk.h: equal-length barcodes as codes on the host, the window and the acceptance rule"""
     _fields_ = [("n_barcodes", C.c_int32), ("length", C.c_int32), ("start", C.c_int32), ("max_mismatches", C.c_int32),
                 ("min_delta", C.c_int32), ("codes", C.c_void_p)]
+
+
+MATES_MAX_LEN = 512
+
+
+class MatesParams(C.Structure):
+    """bnpk_mates_params of include/bnpk.h: when two mates overlap well enough, and the quality cap of the consensus"""
+    _fields_ = [("min_overlap", C.c_int32), ("max_mismatches", C.c_int32), ("max_mismatch_percent", C.c_int32),
+                ("read_through", C.c_int32), ("quality_cap", C.c_int32)]
 
 
 for _name, (_res, _args) in SIGNATURES.items():

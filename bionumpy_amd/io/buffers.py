@@ -258,7 +258,12 @@ class OneLineBuffer(FileBuffer):
         if column.encoding == BaseEncoding:
             return column._flat_data(), column.offsets(), 0
         total = column.total()
-        from ..encoded_array import packed_words
+        from ..encoded_array import packed_words, AlphabetEncoding
+        if isinstance(column.encoding, AlphabetEncoding) and not column.encoding._is_dna():
+            # any other alphabet (the n of ACGTn: merged pairs) has codes of its own: its letters through the look-up kernel
+            letters = np.full(256, 255, dtype=np.uint8)
+            letters[:column.encoding.alphabet_size] = column.encoding._alphabet
+            return get_ops().lut_bytes(column._as_plain(column._data), letters, str(column.encoding)), column.offsets(), 0
         return get_ops().unpack_codes(packed_words(column._data), total, to_ascii=True), column.offsets(), 0
 
     @classmethod

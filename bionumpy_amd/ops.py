@@ -564,6 +564,48 @@ class HipOps:
                        ptr(dist), ptr(second), self._s()))
         return tuple(HArray(dev=t) for t in (index, dist, second))
 
+    @staticmethod
+    def _mates_params(min_overlap, max_mismatches, max_mismatch_percent, read_through, quality_cap=41):
+        return _native.MatesParams(int(min_overlap), int(max_mismatches), int(max_mismatch_percent), 1 if read_through else 0,
+                                   int(quality_cap))
+
+    def mates_overlap(self, data1, offsets1, total1, data2, offsets2, total2, n_rows, min_overlap, max_mismatches,
+                      max_mismatch_percent, read_through, packed):
+        """(length int64, overlap int32, mismatches int32), one entry per pair: the fragment length at the best overlap of row i
+        of the first row set with the reverse complement of row i of the second, -1 where they do not overlap well enough
+        (bnpk_mates_overlap_packed on 2-bit words, else bnpk_mates_overlap_bytes on code bytes).  A mate beyond
+        ``_native.MATES_MAX_LEN`` symbols raises NotImplementedError"""
+        desc = self._mates_params(min_overlap, max_mismatches, max_mismatch_percent, read_through)
+        length, overlap, mismatches = self._empty(n_rows, np.int64), self._empty(n_rows, np.int32), self._empty(n_rows, np.int32)
+        cell = self._err_cell() if n_rows else None
+        call = lib.bnpk_mates_overlap_packed if packed else lib.bnpk_mates_overlap_bytes
+        self._chk(call(self.ctx, C.byref(desc), ptr(data1.dev()) if total1 else None, total1, ptr(offsets1.dev()),
+                       ptr(data2.dev()) if total2 else None, total2, ptr(offsets2.dev()), n_rows, ptr(length), ptr(overlap),
+                       ptr(mismatches), ptr(cell), self._s()))
+        if n_rows:
+            pair = self._fetch(cell, 1)[0]
+            if pair != NONE:
+                raise NotImplementedError("pair %d has a mate of more than %d symbols: not on the MI355X path"
+                                          % (pair, _native.MATES_MAX_LEN))
+        return tuple(HArray(dev=t) for t in (length, overlap, mismatches))
+
+    def mates_merge(self, data1, offsets1, qual1, data2, offsets2, qual2, n_rows, length, quality_cap, packed):
+        """(codes uint8, qualities uint8 | None, offsets int64[n_rows + 1], total): the consensus rows of the pairs with
+        ``length`` >= 0 back to back, the others empty (bnpk_mates_lengths, bnpk_exclusive_scan_i64, bnpk_mates_merge_*)"""
+        desc = self._mates_params(1, 0, 0, True, quality_cap)
+        lens = self._empty(n_rows, np.int64)
+        self._chk(lib.bnpk_mates_lengths(self.ctx, ptr(length.dev()), n_rows, ptr(lens), self._s()))
+        out_off = self.exclusive_scan(HArray(dev=lens))
+        total = self._fetch(out_off.dev()[n_rows:], 1)[0]
+        codes = self._empty(total, np.uint8)
+        qual = self._empty(total, np.uint8) if qual1 is not None else None
+        call = lib.bnpk_mates_merge_packed if packed else lib.bnpk_mates_merge_bytes
+        if total:                                            # (no pair merged: nothing to write, and the parameters are fixed above)
+            self._chk(call(self.ctx, C.byref(desc), ptr(data1.dev()), ptr(offsets1.dev()), None if qual1 is None else ptr(qual1.dev()),
+                           ptr(data2.dev()), ptr(offsets2.dev()), None if qual2 is None else ptr(qual2.dev()), n_rows,
+                           ptr(length.dev()), ptr(out_off.dev()), ptr(codes), ptr(qual), self._s()))
+        return HArray(dev=codes), None if qual is None else HArray(dev=qual), out_off, total
+
     def col_sums_u8(self, data, offsets, n_rows, total, n_cols):
         """(sums int64[n_cols], counts int64[n_cols]) over the columns of ragged uint8 rows"""
         sums, counts = self._empty(n_cols, np.int64), self._empty(n_cols, np.int64)

@@ -19,8 +19,11 @@ from . import approximate
 from .approximate import find_approximate, trim_adapters, ApproxScan
 from . import barcodes
 from .barcodes import assign_barcodes, BarcodeAssignment
+from . import mates
+from .mates import find_mate_overlaps, merge_pairs, MateOverlaps, MergedPairs
 
 __all__ = ["get_kmers", "count_kmers", "KmerEncoder", "Minimizers", "PositionWeightMatrix", "get_minimizers", "get_reverse_complement", "translate_dna_to_protein", "translate", "match_string", "string_matcher", "PWM", "get_motif_scores", "scan_motifs", "MotifScan", "position_weight_matrix", "count_encoded", "EncodedCounts", "SparseKmerCounts",
            "KmerIndex", "KmerLookup", "indexing", "debruin", "DeBruijnGraph", "ColoredDeBruijnGraph",
            "bloom_filter", "BloomFilter", "approximate", "find_approximate", "trim_adapters", "ApproxScan",
-           "barcodes", "assign_barcodes", "BarcodeAssignment"]
+           "barcodes", "assign_barcodes", "BarcodeAssignment",
+           "mates", "find_mate_overlaps", "merge_pairs", "MateOverlaps", "MergedPairs"]

@@ -698,6 +698,68 @@ int bnpk_demux_rows_packed(bnpk_ctx* ctx, const bnpk_demux_library* h_lib, const
 int bnpk_demux_rows_bytes(bnpk_ctx* ctx, const bnpk_demux_library* h_lib, const uint8_t* d_codes, int64_t n, const int64_t* d_offsets,
                           int64_t n_rows, int32_t* d_index, uint8_t* d_dist, uint8_t* d_second, void* stream);
 
+/* ---- paired-end read merging: where the two mates of a fragment overlap, and the consensus read ------------------------------
+ * h is HOST memory.  Row i of the first row set (d_offsets1) and row i of the second (d_offsets2) are the mates of pair i; both
+ * row sets are compact (d_offsets[0] == 0, d_offsets[n_rows] == the number of symbols).
+ *   a = mate 1, n1 symbols.  b = the reverse complement of mate 2, n2 symbols: b[j] = complement(mate2[n2 - 1 - j]), where the
+ *   complement of a code c < 4 is 3 - c and a code >= 4 (_bytes only: N, or anything else) stays what it is.  b is never written
+ *   to memory.  A code >= 4 differs from every symbol, itself included.
+ *   For an integer offset s, which may be negative, b[j] faces a[s + j].  The overlap columns are t in [max(0, s), min(n1, s + n2)),
+ *   ov(s) their number, mm(s) the number of them whose symbols differ, and f = s + n2 the fragment length.
+ *   s is a candidate when ov(s) >= min_overlap and, with read_through == 0, also s >= 0 and s + n2 >= n1 (neither mate runs
+ *   past the other's start).  It qualifies when mm(s) <= max_mismatches and 100 * mm(s) <= max_mismatch_percent * ov(s), in
+ *   integers.  Chosen: the qualifying offset with the largest ov, among those the smallest mm, among those the smallest s.
+ * bnpk_mates_overlap_*: one entry per pair —
+ *     d_length (int64)      f of the chosen offset, -1 where no offset qualifies
+ *     d_overlap (int32)     ov of the chosen offset, 0 where none
+ *     d_mismatches (int32)  mm of the chosen offset, 0 where none
+ *   A pair with an empty mate is never merged.  A pair with a mate of more than BNPK_MATES_MAX_LEN symbols is not looked at: its
+ *   entries are -1, 0, 0 and the smallest such pair index is left in *d_error (device, atomic minimum; the caller stores
+ *   BNPK_NONE there before the call and must treat any other value afterwards as the failure of the call).  The lengths are
+ *   taken from the offsets the kernel reads anyway: no pass of its own.
+ * bnpk_mates_lengths: d_out[i] = max(d_length[i], 0), the symbols pair i contributes to the merged rows; d_out_offsets of
+ *   bnpk_mates_merge_* is bnpk_exclusive_scan_i64 of it.
+ * bnpk_mates_merge_*: pair i with f = d_length[i] >= 0, s = f - n2, writes f columns at d_out_codes + d_out_offsets[i] (and
+ *   d_out_qual, if given); other pairs write nothing.  Column t is covered by a when t < n1 and by b when t >= s, with symbol and
+ *   quality from position t - s of b: mate 2's qualities are reversed with it.  d_qual1 / d_qual2 (uint8 per symbol, the row
+ *   offsets of their sequences) are both NULL or both given; without them every quality counts as 0 and d_out_qual is not written.
+ *     one mate covers the column        its symbol and quality
+ *     both, equal symbols < 4           the symbol, quality min(qa + qb, quality_cap)
+ *     both, different symbols < 4       the symbol of the higher quality, a's on a tie; quality hi - lo
+ *     both, exactly one symbol >= 4     the other symbol with its own quality, whatever the qualities
+ *     both symbols >= 4                 a's symbol and quality
+ *   A column neither mate covers (no d_length that bnpk_mates_overlap_* wrote has one) is written as 0; nothing outside the
+ *   two rows is ever read.  d_out_codes holds codes: 0 .. 3 from _packed, the input's codes from _bytes.
+ * BNPK_ERR_ARG, before anything is launched and also when n_rows == 0: min_overlap < 1, max_mismatches < 0,
+ *   max_mismatch_percent outside 0 .. 100, read_through outside 0 .. 1, quality_cap outside 0 .. 93, one quality pointer of
+ *   the two, a missing pointer.  n_rows == 0 is otherwise BNPK_OK with nothing launched.  _packed: 2-bit bases in the
+ *   bnpk_gather_encode_dna layout.  _bytes: one code per symbol.  Asynchronous on `stream`; no scratch. */
+#define BNPK_MATES_MAX_LEN 512
+typedef struct {
+  int32_t min_overlap;           /* >= 1 */
+  int32_t max_mismatches;        /* >= 0 */
+  int32_t max_mismatch_percent;  /* 0 .. 100 */
+  int32_t read_through;          /* 0: the fragment is at least as long as either mate; 1: a mate may run past the other's start */
+  int32_t quality_cap;           /* 0 .. 93: the largest quality of an agreeing column */
+} bnpk_mates_params;
+int bnpk_mates_overlap_packed(bnpk_ctx* ctx, const bnpk_mates_params* h, const uint64_t* d_packed1, int64_t n_bases1,
+                              const int64_t* d_offsets1, const uint64_t* d_packed2, int64_t n_bases2, const int64_t* d_offsets2,
+                              int64_t n_rows, int64_t* d_length, int32_t* d_overlap, int32_t* d_mismatches, int64_t* d_error,
+                              void* stream);
+int bnpk_mates_overlap_bytes(bnpk_ctx* ctx, const bnpk_mates_params* h, const uint8_t* d_codes1, int64_t n1,
+                             const int64_t* d_offsets1, const uint8_t* d_codes2, int64_t n2, const int64_t* d_offsets2,
+                             int64_t n_rows, int64_t* d_length, int32_t* d_overlap, int32_t* d_mismatches, int64_t* d_error,
+                             void* stream);
+int bnpk_mates_lengths(bnpk_ctx* ctx, const int64_t* d_length, int64_t n_rows, int64_t* d_out, void* stream);
+int bnpk_mates_merge_packed(bnpk_ctx* ctx, const bnpk_mates_params* h, const uint64_t* d_packed1, const int64_t* d_offsets1,
+                            const uint8_t* d_qual1, const uint64_t* d_packed2, const int64_t* d_offsets2, const uint8_t* d_qual2,
+                            int64_t n_rows, const int64_t* d_length, const int64_t* d_out_offsets, uint8_t* d_out_codes,
+                            uint8_t* d_out_qual, void* stream);
+int bnpk_mates_merge_bytes(bnpk_ctx* ctx, const bnpk_mates_params* h, const uint8_t* d_codes1, const int64_t* d_offsets1,
+                           const uint8_t* d_qual1, const uint8_t* d_codes2, const int64_t* d_offsets2, const uint8_t* d_qual2,
+                           int64_t n_rows, const int64_t* d_length, const int64_t* d_out_offsets, uint8_t* d_out_codes,
+                           uint8_t* d_out_qual, void* stream);
+
 /* Same hashes as bnpk_kmers, but never materialised in row order: written exactly once, already partitioned (not
  * stably) by the `bits`-bit digit at bit `shift` (bits <= bnpk_radix_max_bits()) — level 1 of the MSD radix
  * partition of the sparse histogram fused into the generation (bionumpy/sequence/kmers.py:121-126 + the
