@@ -9,6 +9,7 @@ from . import _native  # noqa: F401  (fails loudly if libbnpk.so is missing)
 from .encoded_array import (EncodedArray, EncodedRaggedArray, as_encoded_array, change_encoding, BaseEncoding,
                             DNAEncoding, ACGTEncoding, AlphabetEncoding, QualityEncoding, ACTGEncoding, ACTGnEncoding,
                             ACGTnEncoding, DigitEncoding, ACUGEncoding, RNAENcoding, AminoAcidEncoding, BamEncoding,
+                            CigarOpEncoding,
                             OneToOneEncoding)
 from .ragged import RaggedArray, RaggedShape
 from .exceptions import FormatException, EncodingError
@@ -19,7 +20,7 @@ from .sequence.debruin import DeBruijnGraph, ColoredDeBruijnGraph
 from .sequence import (match_string, get_motif_scores, scan_motifs, get_reverse_complement, get_kmers, count_kmers, get_minimizers, count_encoded, EncodedCounts, SparseKmerCounts,
                        KmerIndex, KmerLookup, KmerEncoder, Minimizers, PositionWeightMatrix, PWM, BloomFilter,
                        find_approximate, trim_adapters, ApproxScan, assign_barcodes, BarcodeAssignment,
-                       find_mate_overlaps, merge_pairs, MateOverlaps, MergedPairs)
+                       find_mate_overlaps, merge_pairs, MateOverlaps, MergedPairs, align_pairs, PairwiseAlignments)
 from .streams import streamable, bincount, histogram, mean, quantile
 from .memory_mapping import MemMapEncodedRaggedArray
 from .datatypes import SequenceEntry, SequenceEntryWithQuality, replace

@@ -150,6 +150,9 @@ SIGNATURES = {
     "bnpk_mates_lengths": (_int, [_p, _p, _i64, _p, _p]),
     "bnpk_mates_merge_packed": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p]),
     "bnpk_mates_merge_bytes": (_int, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p]),
+    "bnpk_align_pairs_packed": (_int, [_p, _p, _p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "bnpk_align_pairs_bytes": (_int, [_p, _p, _p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "bnpk_align_cigar": (_int, [_p, _p, _p, _i64, _p, _p, _p]),
     "bnpk_kmers_partition": (_int, [_p, _p, _p, _i64, _int, _int, _int, _int, _p, _p, _p]),
     "bnpk_minimizers": (_int, [_p, _p, _p, _p, _i64, _i64, _int, _int, _p, _p]),
     "bnpk_count_bytes": (_int, [_p, _p, _i64, _int, _p, _p]),
@@ -237,6 +240,15 @@ class MatesParams(C.Structure):
     """bnpk_mates_params of include/bnpk.h: when two mates overlap well enough, and the quality cap of the consensus"""
     _fields_ = [("min_overlap", C.c_int32), ("max_mismatches", C.c_int32), ("max_mismatch_percent", C.c_int32),
                 ("read_through", C.c_int32), ("quality_cap", C.c_int32)]
+
+
+ALIGN_MAX_LEN, ALIGN_PATH_WORDS, ALIGN_MODES = 512, 65, ("local", "semiglobal", "global")
+
+
+class AlignParams(C.Structure):
+    """bnpk_align_params of include/bnpk.h: the scoring of a pairwise alignment, its mode and whether the path is wanted"""
+    _fields_ = [("alphabet_size", C.c_int32), ("mode", C.c_int32), ("gap_open", C.c_int32), ("gap_extend", C.c_int32),
+                ("traceback", C.c_int32), ("reserved", C.c_int32), ("matrix", C.c_void_p)]
 
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -258,6 +258,7 @@ ACUGEncoding = AlphabetEncoding("ACUG")
 RNAENcoding = ACUGEncoding
 AminoAcidEncoding = AlphabetEncoding("ACDEFGHIKLMNPQRSTVWY*")
 BamEncoding = AlphabetEncoding("=ACMGRSVTWYHKDBN")
+CigarOpEncoding = AlphabetEncoding("MIDNSHP=X")          # SAM's op order: what sequence/alignment.py writes its CIGARs under
 
 
 class _PackedDna:

@@ -606,6 +606,53 @@ class HipOps:
                            ptr(length.dev()), ptr(out_off.dev()), ptr(codes), ptr(qual), self._s()))
         return HArray(dev=codes), None if qual is None else HArray(dev=qual), out_off, total
 
+    align_batch_pairs = 1 << 21          # pairs per traceback call: a batch's path slots (260 bytes a pair) are what it bounds
+
+    def align_pairs(self, qdata, qoffsets, qtotal, tdata, toffsets, ttotal, n_rows, n_targets, matrix, gap_open, gap_extend, mode,
+                    traceback, packed):
+        """(score, query_end, target_end, query_start, target_start, cigar) — int32 per pair, the starts None without
+        ``traceback``; cigar = (ops uint8, lengths int32, runs int64 per pair, offsets int64[n_rows + 1], total) or None: row i of
+        the queries aligned with row i of the targets, or with their only row (bnpk_align_pairs_packed on 2-bit words, else
+        bnpk_align_pairs_bytes on code bytes; bnpk_exclusive_scan_i64 and bnpk_align_cigar per batch of ``align_batch_pairs``).
+        ``matrix``: integers [query code][target code]; ``mode``: an index into ``_native.ALIGN_MODES``.  A row beyond
+        ``_native.ALIGN_MAX_LEN`` symbols raises NotImplementedError"""
+        matrix = np.ascontiguousarray(matrix, dtype=np.int32)
+        desc = _native.AlignParams(matrix.shape[0], int(mode), int(gap_open), int(gap_extend), 1 if traceback else 0, 0,
+                                   matrix.ctypes.data)
+        score, qend, tend = (self._empty(n_rows, np.int32) for _ in range(3))
+        qstart, tstart = (self._empty(n_rows, np.int32) if traceback else None for _ in range(2))
+        runs = self._empty(n_rows, np.int64) if traceback else None
+        cell = self._err_cell() if n_rows else None
+        call = lib.bnpk_align_pairs_packed if packed else lib.bnpk_align_pairs_bytes
+        batch = max(1, int(self.align_batch_pairs)) if traceback else max(1, n_rows)
+        pieces = []
+        for first in range(0, max(1, n_rows), batch):        # (no rows: one call, for the check of the arguments)
+            count = min(batch, n_rows - first)
+            paths = self._empty(count * _native.ALIGN_PATH_WORDS, np.int32) if traceback else None
+            self._chk(call(self.ctx, C.byref(desc), ptr(qdata.dev()) if qtotal else None, qtotal, ptr(qoffsets.dev()),
+                           ptr(tdata.dev()) if ttotal else None, ttotal, ptr(toffsets.dev()), n_targets, n_rows, first, count,
+                           ptr(score), ptr(qend), ptr(tend), ptr(qstart), ptr(tstart), ptr(runs), ptr(paths), ptr(cell), self._s()))
+            if traceback and count:
+                run_off = self.exclusive_scan(HArray(dev=runs[first:first + count])).dev()
+                n_runs = self._fetch(run_off[count:], 1)[0]
+                piece = self._empty(n_runs, np.uint8), self._empty(n_runs, np.int32)
+                if n_runs:
+                    self._chk(lib.bnpk_align_cigar(self.ctx, ptr(paths), ptr(run_off), count, ptr(piece[0]), ptr(piece[1]), self._s()))
+                pieces.append(piece)
+        if n_rows:
+            pair = self._fetch(cell, 1)[0]
+            if pair != NONE:
+                raise NotImplementedError("pair %d has a row of more than %d symbols: not on the MI355X path"
+                                          % (pair, _native.ALIGN_MAX_LEN))
+        cigar = None
+        if traceback:
+            ops_, lens_ = ([p[i] for p in pieces] for i in range(2))
+            ops_, lens_ = (x[0] if len(x) == 1 else self.device.torch_cat(x) if x else self._empty(0, d)
+                           for x, d in ((ops_, np.uint8), (lens_, np.int32)))
+            offsets = self.exclusive_scan(HArray(dev=runs))
+            cigar = (HArray(dev=ops_), HArray(dev=lens_), HArray(dev=runs), offsets, int(ops_.numel()))
+        return tuple(None if t is None else HArray(dev=t) for t in (score, qend, tend, qstart, tstart)) + (cigar,)
+
     def col_sums_u8(self, data, offsets, n_rows, total, n_cols):
         """(sums int64[n_cols], counts int64[n_cols]) over the columns of ragged uint8 rows"""
         sums, counts = self._empty(n_cols, np.int64), self._empty(n_cols, np.int64)

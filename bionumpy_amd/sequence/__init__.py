@@ -21,9 +21,12 @@ from . import barcodes
 from .barcodes import assign_barcodes, BarcodeAssignment
 from . import mates
 from .mates import find_mate_overlaps, merge_pairs, MateOverlaps, MergedPairs
+from . import alignment
+from .alignment import align_pairs, PairwiseAlignments, count_reference_length
 
 __all__ = ["get_kmers", "count_kmers", "KmerEncoder", "Minimizers", "PositionWeightMatrix", "get_minimizers", "get_reverse_complement", "translate_dna_to_protein", "translate", "match_string", "string_matcher", "PWM", "get_motif_scores", "scan_motifs", "MotifScan", "position_weight_matrix", "count_encoded", "EncodedCounts", "SparseKmerCounts",
            "KmerIndex", "KmerLookup", "indexing", "debruin", "DeBruijnGraph", "ColoredDeBruijnGraph",
            "bloom_filter", "BloomFilter", "approximate", "find_approximate", "trim_adapters", "ApproxScan",
            "barcodes", "assign_barcodes", "BarcodeAssignment",
-           "mates", "find_mate_overlaps", "merge_pairs", "MateOverlaps", "MergedPairs"]
+           "mates", "find_mate_overlaps", "merge_pairs", "MateOverlaps", "MergedPairs",
+           "alignment", "align_pairs", "PairwiseAlignments", "count_reference_length"]

@@ -760,6 +760,67 @@ int bnpk_mates_merge_bytes(bnpk_ctx* ctx, const bnpk_mates_params* h, const uint
                            int64_t n_rows, const int64_t* d_length, const int64_t* d_out_offsets, uint8_t* d_out_codes,
                            uint8_t* d_out_qual, void* stream);
 
+/* ---- pairwise alignment with affine gaps: score, ends, and the path as a CIGAR ----------------------------------------------------
+ * h and what it points at are HOST memory.  Row i of the queries (d_offsets_q) is aligned with row i of the targets
+ * (d_offsets_t), or with the targets' only row when n_targets == 1; both row sets are compact.  Take the query q[0 .. n) and the
+ * target t[0 .. m), S = h->matrix ([query code][target code], alphabet_size x alphabet_size), go = gap_open, ge = gap_extend: a
+ * gap of L columns costs go + L * ge.  In exact integers, with -infinity where a term does not exist:
+ *     E[i][j] = max(H[i][j-1] - go - ge, E[i][j-1] - ge)      j >= 1      (a target symbol against a gap: D)
+ *     F[i][j] = max(H[i-1][j] - go - ge, F[i-1][j] - ge)      i >= 1      (a query symbol against a gap: I)
+ *     H[i][j] = max(H[i-1][j-1] + S[q[i-1]][t[j-1]]  (i, j >= 1),  E[i][j],  F[i][j],  0 if local)
+ *     H[0][0] = 0;  local: H[i][0] = H[0][j] = 0;  semiglobal: H[0][j] = 0;  everything else by the recurrences
+ *   End.  BNPK_ALIGN_GLOBAL: (n, m).  BNPK_ALIGN_SEMIGLOBAL (the whole query, free ends in the target): the largest H[n][j], the
+ *   smallest j among equals.  BNPK_ALIGN_LOCAL: the largest H[i][j], the smallest i among equals and then the smallest j; a best
+ *   score of 0 is the empty alignment at (0, 0).  d_score = H at the end, d_query_end = i, d_target_end = j (half-open,
+ *   row-relative).
+ *   Path (h->traceback != 0).  Walk from the end in state H.  In state H at (i, j) stop when: local, H = 0; semiglobal, i = 0;
+ *   global, i = j = 0.  Otherwise prefer the diagonal (i, j >= 1 and H = H[i-1][j-1] + S: M, to H at (i-1, j-1)), then E
+ *   (H = E[i][j]), then F.  State E at (i, j) is one D and goes to H at (i, j-1) if E[i][j] = H[i][j-1] - go - ge (opening is
+ *   preferred over extending), else to E at (i, j-1); state F likewise with I and (i-1, j).  d_query_start / d_target_start are
+ *   where the walk stops, the CIGAR is the walk reversed and run-length encoded: ops 0 = M, 1 = I (consumes the query), 2 = D
+ *   (consumes the target) — SAM's numbering.  Nothing else is emitted.
+ * bnpk_align_pairs_*: the pairs first .. first + n_pairs - 1 of n_rows (a batch; every d_ output has n_rows entries and is
+ *   indexed by the pair).  With traceback, d_runs[pair] (int64) is the number of CIGAR runs, and d_paths, n_pairs slots of
+ *   BNPK_ALIGN_PATH_WORDS uint32 each (slot pair - first), holds the walk at 2 bits per step and its length; without, d_query_start,
+ *   d_target_start, d_runs and d_paths are not touched and may be NULL.  The batch is what bounds d_paths: every output is the
+ *   same for every split into batches.
+ * bnpk_align_cigar: with d_run_offsets = bnpk_exclusive_scan_i64 of d_runs[first .. first + n_pairs), writes the runs of pair
+ *   first + p at d_ops / d_lengths + d_run_offsets[p], in order.
+ * A pair with a row of more than BNPK_ALIGN_MAX_LEN symbols is not aligned: its entries are 0, no runs, and the smallest such
+ *   pair index is left in *d_error (device, atomic minimum; the caller stores BNPK_NONE there before the call).
+ * BNPK_ERR_ARG, before anything is launched and also when n_rows == 0: mode outside 0 .. 2, gap_open or gap_extend outside
+ *   0 .. 127, a matrix entry outside -128 .. 127, alphabet_size other than 4 (_packed) or outside 1 .. BNPK_APPROX_MAX_ALPHABET
+ *   (_bytes), n_targets other than n_rows or 1, a batch outside the rows, a missing pointer.  _packed: 2-bit bases in the
+ *   bnpk_gather_encode_dna layout.  _bytes: one code per symbol; a code >= alphabet_size scores the smallest entry of the matrix
+ *   against everything and reads nothing outside the matrix.  Asynchronous on `stream` (the matrix is copied before the call
+ *   returns); scratch from the ctx arena: 4 bytes per pair of the batch. */
+#define BNPK_ALIGN_MAX_LEN     512
+#define BNPK_ALIGN_PATH_WORDS  65
+#define BNPK_ALIGN_LOCAL       0
+#define BNPK_ALIGN_SEMIGLOBAL  1
+#define BNPK_ALIGN_GLOBAL      2
+typedef struct {
+  int32_t alphabet_size;   /* A: 4 for _packed, 1 .. BNPK_APPROX_MAX_ALPHABET for _bytes */
+  int32_t mode;            /* BNPK_ALIGN_LOCAL / _SEMIGLOBAL / _GLOBAL */
+  int32_t gap_open;        /* 0 .. 127 */
+  int32_t gap_extend;      /* 0 .. 127 */
+  int32_t traceback;       /* 0: score and ends only */
+  int32_t reserved;
+  const int32_t* matrix;   /* HOST, A * A entries in -128 .. 127, [query code][target code] */
+} bnpk_align_params;
+int bnpk_align_pairs_packed(bnpk_ctx* ctx, const bnpk_align_params* h, const uint64_t* d_packed_q, int64_t n_bases_q,
+                            const int64_t* d_offsets_q, const uint64_t* d_packed_t, int64_t n_bases_t, const int64_t* d_offsets_t,
+                            int64_t n_targets, int64_t n_rows, int64_t first, int64_t n_pairs, int32_t* d_score,
+                            int32_t* d_query_end, int32_t* d_target_end, int32_t* d_query_start, int32_t* d_target_start,
+                            int64_t* d_runs, uint32_t* d_paths, int64_t* d_error, void* stream);
+int bnpk_align_pairs_bytes(bnpk_ctx* ctx, const bnpk_align_params* h, const uint8_t* d_codes_q, int64_t n_q,
+                           const int64_t* d_offsets_q, const uint8_t* d_codes_t, int64_t n_t, const int64_t* d_offsets_t,
+                           int64_t n_targets, int64_t n_rows, int64_t first, int64_t n_pairs, int32_t* d_score,
+                           int32_t* d_query_end, int32_t* d_target_end, int32_t* d_query_start, int32_t* d_target_start,
+                           int64_t* d_runs, uint32_t* d_paths, int64_t* d_error, void* stream);
+int bnpk_align_cigar(bnpk_ctx* ctx, const uint32_t* d_paths, const int64_t* d_run_offsets, int64_t n_pairs, uint8_t* d_ops,
+                     int32_t* d_lengths, void* stream);
+
 /* Same hashes as bnpk_kmers, but never materialised in row order: written exactly once, already partitioned (not
  * stably) by the `bits`-bit digit at bit `shift` (bits <= bnpk_radix_max_bits()) — level 1 of the MSD radix
  * partition of the sparse histogram fused into the generation (bionumpy/sequence/kmers.py:121-126 + the
