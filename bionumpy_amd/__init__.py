@@ -20,7 +20,8 @@ from .sequence.debruin import DeBruijnGraph, ColoredDeBruijnGraph
 from .sequence import (match_string, get_motif_scores, scan_motifs, get_reverse_complement, get_kmers, count_kmers, get_minimizers, count_encoded, EncodedCounts, SparseKmerCounts,
                        KmerIndex, KmerLookup, KmerEncoder, Minimizers, PositionWeightMatrix, PWM, BloomFilter,
                        find_approximate, trim_adapters, ApproxScan, assign_barcodes, BarcodeAssignment,
-                       find_mate_overlaps, merge_pairs, MateOverlaps, MergedPairs, align_pairs, PairwiseAlignments)
+                       find_mate_overlaps, merge_pairs, MateOverlaps, MergedPairs, align_pairs, PairwiseAlignments,
+                       SeedIndex, place_reads, Placements)
 from .streams import streamable, bincount, histogram, mean, quantile
 from .memory_mapping import MemMapEncodedRaggedArray
 from .datatypes import SequenceEntry, SequenceEntryWithQuality, replace

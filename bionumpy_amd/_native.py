@@ -153,6 +153,12 @@ SIGNATURES = {
     "bnpk_align_pairs_packed": (_int, [_p, _p, _p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "bnpk_align_pairs_bytes": (_int, [_p, _p, _p, _i64, _p, _p, _i64, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p, _p]),
     "bnpk_align_cigar": (_int, [_p, _p, _p, _i64, _p, _p, _p]),
+    "bnpk_seed_table_bits": (_int, [_i64, _int]),
+    "bnpk_seed_index_positions": (_int, [_p, _p, _p, _i64, _i64, _p, _p]),
+    "bnpk_seed_index_finish": (_int, [_p, _p, _i64, _p, _i64, _int, _int, _p, _p, _p]),
+    "bnpk_seed_place_packed": (_int, [_p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _p, _p, _p, _i64, _p, _p, _p, _p, _p, _p, _p]),
+    "bnpk_seed_window_lengths": (_int, [_p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _p, _p, _p]),
+    "bnpk_seed_windows_packed": (_int, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _p, _p]),
     "bnpk_kmers_partition": (_int, [_p, _p, _p, _i64, _int, _int, _int, _int, _p, _p, _p]),
     "bnpk_minimizers": (_int, [_p, _p, _p, _p, _i64, _i64, _int, _int, _p, _p]),
     "bnpk_count_bytes": (_int, [_p, _p, _i64, _int, _p, _p]),
@@ -249,6 +255,15 @@ class AlignParams(C.Structure):
     """bnpk_align_params of include/bnpk.h: the scoring of a pairwise alignment, its mode and whether the path is wanted"""
     _fields_ = [("alphabet_size", C.c_int32), ("mode", C.c_int32), ("gap_open", C.c_int32), ("gap_extend", C.c_int32),
                 ("traceback", C.c_int32), ("reserved", C.c_int32), ("matrix", C.c_void_p)]
+
+
+SEED_MIN_K, SEED_MAX_K, SEED_MAX_LEN, SEED_MAX_HITS, SEED_MAX_OCCURRENCES, SEED_MAX_BAND = 8, 31, 512, 4096, 2048, 256
+
+
+class SeedParams(C.Structure):
+    """bnpk_seed_params of include/bnpk.h: how the reads are placed on a k-mer position index"""
+    _fields_ = [("k", C.c_int32), ("max_occurrences", C.c_int32), ("band", C.c_int32), ("min_votes", C.c_int32),
+                ("table_bits", C.c_int32), ("reserved", C.c_int32)]
 
 
 for _name, (_res, _args) in SIGNATURES.items():

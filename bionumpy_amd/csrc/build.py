@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 LIB = os.path.join(HERE, "libbnpk.so")
 OBJ_DIR = os.path.join(HERE, "build")
-SOURCES = ["api.hip", "scan.hip", "decode.hip", "multiline.hip", "fastq.hip", "encode.hip", "kmers.hip", "revcomp.hip", "translate.hip", "motif.hip", "bloom.hip", "pwm_rows.hip", "approx.hip", "demux.hip", "mates.hip", "align.hip", "rowops.hip", "radix.hip", "finish.hip", "finish_dup.hip", "finish_wave.hip", "finish_multi.hip", "finish_small.hip", "merge.hip", "count.hip", "sparse.hip", "synth.hip", "collectives.hip"]
+SOURCES = ["api.hip", "scan.hip", "decode.hip", "multiline.hip", "fastq.hip", "encode.hip", "kmers.hip", "revcomp.hip", "translate.hip", "motif.hip", "bloom.hip", "pwm_rows.hip", "approx.hip", "demux.hip", "mates.hip", "align.hip", "seeds.hip", "rowops.hip", "radix.hip", "finish.hip", "finish_dup.hip", "finish_wave.hip", "finish_multi.hip", "finish_small.hip", "merge.hip", "count.hip", "sparse.hip", "synth.hip", "collectives.hip"]
 LINT = os.path.join(HERE, "isa_lint.py")
 HEADERS = [os.path.join(HERE, "common.h"), os.path.join(HERE, "scan.h"), os.path.join(HERE, "rows.h"),
            os.path.join(HERE, "kmer_gen.h"), os.path.join(HERE, "finish.h"),
@@ -27,7 +27,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # the older objects keep the flags they were measured with.  bloom.hip is integer code: its ISA is the same either way today
 # (NOTES.md, "Blocked Bloom filter"); pwm_rows.hip adds in float64 only (V_ADD_F64 is not one of the three).  The host pass of hipcc does not know the feature and says so once per pass; harmless.
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-EXTRA_FLAGS = {"bloom.hip": NO_PK_F32, "pwm_rows.hip": NO_PK_F32, "approx.hip": NO_PK_F32, "demux.hip": NO_PK_F32, "mates.hip": NO_PK_F32, "align.hip": NO_PK_F32}
+EXTRA_FLAGS = {"bloom.hip": NO_PK_F32, "pwm_rows.hip": NO_PK_F32, "approx.hip": NO_PK_F32, "demux.hip": NO_PK_F32, "mates.hip": NO_PK_F32, "align.hip": NO_PK_F32, "seeds.hip": NO_PK_F32}
 
 
 def _hipcc():

@@ -653,6 +653,58 @@ class HipOps:
             cigar = (HArray(dev=ops_), HArray(dev=lens_), HArray(dev=runs), offsets, int(ops_.numel()))
         return tuple(None if t is None else HArray(dev=t) for t in (score, qend, tend, qstart, tstart)) + (cigar,)
 
+    def seed_index(self, packed, offsets, lens, n_rows, total, k):
+        """(keys int64[U], starts int64[U + 1], positions int32[N], table int32[2^bits + 1], bits): the k-mer position index of
+        compact 2-bit rows as include/bnpk.h defines it — bnpk_kmers, bnpk_seed_index_positions, the (k-mer, coordinate) pairs in
+        order by ``unique_pairs``, their runs by bnpk_run_heads, then bnpk_seed_index_finish (int32 coordinates, prefix table)"""
+        out_off, n = self.row_offsets(lens, k) if n_rows else (None, 0)
+        if n:
+            hashes = self.kmers(packed, offsets, out_off, n_rows, n, k, total)
+            where = self._empty(n, np.int64)
+            self._chk(lib.bnpk_seed_index_positions(self.ctx, ptr(offsets.dev()), ptr(out_off.dev()), n_rows, n, ptr(where), self._s()))
+            sorted_k, sorted_pos = (x.dev() for x in self.unique_pairs(hashes, HArray(dev=where), key_bits=2 * k, n_values=max(total, 1)))
+            n_keys, tile_off = self._runs(sorted_k)
+            keys, starts = self._empty(n_keys, np.int64), self._empty(n_keys + 1, np.int64)
+            self._chk(lib.bnpk_run_heads(self.ctx, ptr(sorted_k), None, n, ptr(tile_off), n_keys, ptr(keys), None, ptr(starts), self._s()))
+        else:
+            n_keys, keys, sorted_pos, starts = 0, self._empty(0, np.int64), None, self.device.zeros(1, np.int64)
+        bits = int(lib.bnpk_seed_table_bits(n_keys, k))
+        positions, table = self._empty(n, np.int32), self._empty((1 << bits) + 1, np.int32)
+        self._chk(lib.bnpk_seed_index_finish(self.ctx, ptr(keys), n_keys, ptr(sorted_pos), n, k, bits, ptr(positions), ptr(table), self._s()))
+        return HArray(dev=keys), HArray(dev=starts), HArray(dev=positions), HArray(dev=table), bits
+
+    def seed_place(self, packed, offsets, total, n_rows, index, ref_offsets, n_ref_rows, k, max_occurrences, band, min_votes):
+        """(votes, second, strand, row, position), int32 per read: every read placed on the index by votes over seed diagonals
+        (bnpk_seed_place_packed; ``index`` as ``seed_index`` returns it).  A read beyond ``_native.SEED_MAX_LEN`` symbols or
+        ``_native.SEED_MAX_HITS`` possible hits raises NotImplementedError"""
+        keys, starts, positions, table, bits = index
+        desc = _native.SeedParams(int(k), int(max_occurrences), int(band), int(min_votes), bits, 0)
+        out = [self._empty(n_rows, np.int32) for _ in range(5)]
+        cell = self._err_cell() if n_rows else None
+        self._chk(lib.bnpk_seed_place_packed(self.ctx, C.byref(desc), ptr(packed.dev()) if total else None, total, ptr(offsets.dev()), n_rows,
+                                             ptr(keys.dev()), keys.size, ptr(starts.dev()), ptr(positions.dev()), ptr(table.dev()),
+                                             ptr(ref_offsets.dev()), n_ref_rows, *[ptr(t) for t in out], ptr(cell), self._s()))
+        if n_rows:
+            read = self._fetch(cell, 1)[0]
+            if read != NONE:
+                raise NotImplementedError("read %d has more than %d symbols, or more than %d possible hits (2 x k-mers x max_occurrences):"
+                                          " not on the MI355X path" % (read, _native.SEED_MAX_LEN, _native.SEED_MAX_HITS))
+        return tuple(HArray(dev=t) for t in out)
+
+    def seed_windows(self, ref_packed, ref_offsets, n_ref_rows, strand, row, position, offsets, n_rows, pad):
+        """(words int64 — 2-bit bases —, lengths int64, offsets int64[n_rows + 1], total, start int32): the reference window of
+        every placed read, reverse complemented on strand 1 (bnpk_seed_window_lengths, bnpk_exclusive_scan_i64,
+        bnpk_seed_windows_packed)"""
+        lens, start = self._empty(n_rows, np.int64), self._empty(n_rows, np.int32)
+        self._chk(lib.bnpk_seed_window_lengths(self.ctx, ptr(strand.dev()), ptr(row.dev()), ptr(position.dev()), ptr(offsets.dev()),
+                                               ptr(ref_offsets.dev()), n_ref_rows, n_rows, int(pad), ptr(lens), ptr(start), self._s()))
+        out_off = self.exclusive_scan(HArray(dev=lens))
+        total = self._fetch(out_off.dev()[n_rows:], 1)[0]
+        words = self._empty(total // 32 + 2, np.int64)
+        self._chk(lib.bnpk_seed_windows_packed(self.ctx, ptr(ref_packed.dev()) if total else None, ptr(ref_offsets.dev()), ptr(strand.dev()),
+                                               ptr(row.dev()), ptr(start), ptr(out_off.dev()), n_rows, total, ptr(words), self._s()))
+        return HArray(dev=words), HArray(dev=lens), out_off, total, HArray(dev=start)
+
     def col_sums_u8(self, data, offsets, n_rows, total, n_cols):
         """(sums int64[n_cols], counts int64[n_cols]) over the columns of ragged uint8 rows"""
         sums, counts = self._empty(n_cols, np.int64), self._empty(n_cols, np.int64)

@@ -23,10 +23,13 @@ from . import mates
 from .mates import find_mate_overlaps, merge_pairs, MateOverlaps, MergedPairs
 from . import alignment
 from .alignment import align_pairs, PairwiseAlignments, count_reference_length
+from . import seeds
+from .seeds import SeedIndex, place_reads, Placements, ReferenceWindows
 
 __all__ = ["get_kmers", "count_kmers", "KmerEncoder", "Minimizers", "PositionWeightMatrix", "get_minimizers", "get_reverse_complement", "translate_dna_to_protein", "translate", "match_string", "string_matcher", "PWM", "get_motif_scores", "scan_motifs", "MotifScan", "position_weight_matrix", "count_encoded", "EncodedCounts", "SparseKmerCounts",
            "KmerIndex", "KmerLookup", "indexing", "debruin", "DeBruijnGraph", "ColoredDeBruijnGraph",
            "bloom_filter", "BloomFilter", "approximate", "find_approximate", "trim_adapters", "ApproxScan",
            "barcodes", "assign_barcodes", "BarcodeAssignment",
            "mates", "find_mate_overlaps", "merge_pairs", "MateOverlaps", "MergedPairs",
-           "alignment", "align_pairs", "PairwiseAlignments", "count_reference_length"]
+           "alignment", "align_pairs", "PairwiseAlignments", "count_reference_length",
+           "seeds", "SeedIndex", "place_reads", "Placements", "ReferenceWindows"]

@@ -821,6 +821,80 @@ int bnpk_align_pairs_bytes(bnpk_ctx* ctx, const bnpk_align_params* h, const uint
 int bnpk_align_cigar(bnpk_ctx* ctx, const uint32_t* d_paths, const int64_t* d_run_offsets, int64_t n_pairs, uint8_t* d_ops,
                      int32_t* d_lengths, void* stream);
 
+/* ---- seed-and-vote read placement on a k-mer position index, and the windows align_pairs takes ------------------------------------
+ * h is HOST memory.  The reference is R compact rows of 2-bit DNA with row offsets off[0 .. R]; its total length G is less than
+ * 2^31 - 512.  The global coordinate of position x of row r is off[r] + x.  A k-mer's hash is bnpk_kmers' (first base in the
+ * lowest bits), rc(h) the hash of its reverse complement as in bnpk_canonical_kmers; BNPK_SEED_MIN_K <= k <= BNPK_SEED_MAX_K.
+ *   Index of (reference, k).  keys (int64, U entries): the distinct k-mers of all rows, ascending.  starts (int64, U + 1).
+ *   positions (int32, N entries, N the number of k-mers over all rows): positions[starts[u] .. starts[u+1]) are the global
+ *   start coordinates of key u, ascending; occ(key) = starts[u+1] - starts[u].  No k-mer spans two rows.  table (int32,
+ *   2^table_bits + 1 entries, table_bits = bnpk_seed_table_bits(U, k)): table[b] = the number of keys whose top table_bits bits
+ *   (of 2k) are below b — an aid of the lookup, not part of the definition.
+ *   Hits of a read q of L symbols, k <= L <= BNPK_SEED_MAX_LEN.  For every read position p in [0, L - k], h the forward hash of
+ *   the k-mer at p: strand 0 looks up h and, if 1 <= occ(h) <= max_occurrences, every occurrence g is a hit (s = 0, d = g - p, g);
+ *   strand 1 looks up rc(h) and under the same condition every occurrence g is a hit (s = 1, d = g - (L - k - p), g): L - k - p is
+ *   where that k-mer starts in the reverse complement of the read.  A key with more occurrences gives no hits at all.  d is the
+ *   global coordinate at which the read, or its reverse complement, would start.
+ *   Votes.  B = band, a power of two in 1 .. BNPK_SEED_MAX_BAND; bin(d) = floor(d / B) (d may be negative: an arithmetic shift);
+ *   c(s, b) = the number of hits of strand s in bin b.  The candidates are the (s, b) with c(s, b) >= 1, the score of one is
+ *   W(s, b) = c(s, b) + c(s, b + 1) — two neighbouring bins, so that a diagonal next to a bin edge, or an indel of up to B, does
+ *   not split a locus.  The winner is the candidate with the largest W, among equals the smaller s, then the smaller b.
+ *   Outputs, int32 per read.  d_votes: W of the winner, 0 with no hits.  d_second: the largest W among the candidates (s', b')
+ *   with s' != s or |b' - b| >= 2, 0 if there is none.  d_strand: s of the winner.  d_row, d_position: the diagonal D is the
+ *   smallest d among the winner's hits (those of strand s in the bins b and b + 1), the anchor the hit with d = D that has the
+ *   smallest g; d_row is the reference row that contains the anchor's g and d_position = D - off[row], negative when the read
+ *   hangs over the row's start.  A read is placed iff votes >= min_votes (>= 1); otherwise strand = row = -1 and position = 0,
+ *   votes and second keep their values.  A read with L < k has no hits.
+ *   Capacity.  A read with L > BNPK_SEED_MAX_LEN or 2 * (L - k + 1) * max_occurrences > BNPK_SEED_MAX_HITS is not placed: its
+ *   outputs are those of an unplaced read with votes = second = 0, and the smallest such read index is left in *d_error (device,
+ *   atomic minimum; the caller stores BNPK_NONE there before the call).  Reads within the bound are placed exactly; no hit is
+ *   ever dropped.  (A 150-base read at k = 15 may use max_occurrences up to 15, a 512-base read at k = 8 up to 4.)
+ *   Windows.  For a placed read i of L_i symbols, pad >= 0 and len = off[row+1] - off[row]: a = max(0, position - pad),
+ *   b = min(len, position + L_i + pad); the window is reference[row][a .. b), reverse complemented when strand = 1, empty if
+ *   b <= a; d_start = a.  Unplaced reads get an empty window and d_start = 0.
+ * bnpk_seed_index_positions: d_positions[j] (int64) = the global coordinate of k-mer j of bnpk_kmers over the reference
+ *   (d_in_offsets = off, d_out_offsets = bnpk_row_offsets(lens, window=k)).  bnpk_index_build on (k-mer, coordinate) then gives
+ *   the pairs in order and bnpk_run_heads `keys` and `starts`.  bnpk_seed_index_finish narrows the sorted coordinates to int32 and
+ *   fills the table.  bnpk_seed_table_bits is host arithmetic: ~8 keys to an entry, at most min(2k, BNPK_SEED_MAX_TABLE_BITS) bits.
+ * bnpk_seed_place_packed: reads as 2-bit bases in the bnpk_gather_encode_dna layout with their row offsets.
+ * bnpk_seed_window_lengths: d_lengths (int64) and d_start (int32) per read; with d_out_offsets = bnpk_exclusive_scan_i64 of the
+ *   lengths, bnpk_seed_windows_packed writes the windows back to back as 2-bit bases in the same layout (total / 32 + 2 words,
+ *   every one of them written).
+ * BNPK_ERR_ARG, before anything is launched and also when n_reads == 0: k outside BNPK_SEED_MIN_K .. BNPK_SEED_MAX_K,
+ *   max_occurrences outside 1 .. BNPK_SEED_MAX_OCCURRENCES, a band that is not a power of two in 1 .. BNPK_SEED_MAX_BAND,
+ *   min_votes < 1, table_bits outside 1 .. min(2k, BNPK_SEED_MAX_TABLE_BITS), a missing pointer.  Asynchronous on `stream`;
+ *   bnpk_seed_place_packed takes 4 bytes per read from the ctx arena. */
+#define BNPK_SEED_MIN_K            8
+#define BNPK_SEED_MAX_K            31
+#define BNPK_SEED_MAX_LEN          512
+#define BNPK_SEED_MAX_HITS         4096
+#define BNPK_SEED_MAX_OCCURRENCES  2048
+#define BNPK_SEED_MAX_BAND         256
+#define BNPK_SEED_MAX_TABLE_BITS   24
+typedef struct {
+  int32_t k;                 /* BNPK_SEED_MIN_K .. BNPK_SEED_MAX_K: the index's */
+  int32_t max_occurrences;   /* 1 .. BNPK_SEED_MAX_OCCURRENCES */
+  int32_t band;              /* B: a power of two in 1 .. BNPK_SEED_MAX_BAND */
+  int32_t min_votes;         /* >= 1 */
+  int32_t table_bits;        /* the index's: bnpk_seed_table_bits(U, k) */
+  int32_t reserved;
+} bnpk_seed_params;
+int bnpk_seed_table_bits(int64_t n_keys, int k);
+int bnpk_seed_index_positions(bnpk_ctx* ctx, const int64_t* d_in_offsets, const int64_t* d_out_offsets, int64_t n_rows, int64_t n,
+                              int64_t* d_positions, void* stream);
+int bnpk_seed_index_finish(bnpk_ctx* ctx, const int64_t* d_keys, int64_t n_keys, const int64_t* d_positions64, int64_t n, int k,
+                           int table_bits, int32_t* d_positions, int32_t* d_table, void* stream);
+int bnpk_seed_place_packed(bnpk_ctx* ctx, const bnpk_seed_params* h, const uint64_t* d_packed, int64_t n_bases, const int64_t* d_offsets,
+                           int64_t n_reads, const int64_t* d_keys, int64_t n_keys, const int64_t* d_starts, const int32_t* d_positions,
+                           const int32_t* d_table, const int64_t* d_ref_offsets, int64_t n_ref_rows, int32_t* d_votes, int32_t* d_second,
+                           int32_t* d_strand, int32_t* d_row, int32_t* d_position, int64_t* d_error, void* stream);
+int bnpk_seed_window_lengths(bnpk_ctx* ctx, const int32_t* d_strand, const int32_t* d_row, const int32_t* d_position,
+                             const int64_t* d_offsets, const int64_t* d_ref_offsets, int64_t n_ref_rows, int64_t n_reads, int64_t pad,
+                             int64_t* d_lengths, int32_t* d_start, void* stream);
+int bnpk_seed_windows_packed(bnpk_ctx* ctx, const uint64_t* d_ref_packed, const int64_t* d_ref_offsets, const int32_t* d_strand,
+                             const int32_t* d_row, const int32_t* d_start, const int64_t* d_out_offsets, int64_t n_reads, int64_t total,
+                             uint64_t* d_out, void* stream);
+
 /* Same hashes as bnpk_kmers, but never materialised in row order: written exactly once, already partitioned (not
  * stably) by the `bits`-bit digit at bit `shift` (bits <= bnpk_radix_max_bits()) — level 1 of the MSD radix
  * partition of the sparse histogram fused into the generation (bionumpy/sequence/kmers.py:121-126 + the
